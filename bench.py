@@ -14,7 +14,13 @@ Multi-GPU (``torch.distributed.run``, one process per GPU): graphs of a batch ar
 each rank runs its own B=32 graphs with no data-path collective ("scaling": "weak"); time is the
 max over ranks of the barrier-bracketed K steps.
 
-Extra JSON fields:
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, spins up, warms up, times the K
+steps and prints the result line: the headline figure and what describes it, nothing else.
+``--dump-outputs DIR`` also writes what the last timed step returned (``DIR/gcn_out.npy``, float32;
+a fixed seeded sample of the elements when the tensor is larger than ``DUMP_MAX_BYTES``), so two
+builds can be compared output for output: the inputs are seeded and identical from run to run.
+
+Extra JSON fields, measured only with ``--full`` (each takes runs of its own):
 * ``roofline`` — the aggregation kernel alone, timed with HIP events on its stream over back-to-back
   launches; achieved = algorithmic bytes per launch / mean launch time (bytes: DESIGN.md §4).
   ``traffic`` is the PMC-measured HBM bytes per launch (rocprofv3 FETCH_SIZE/WRITE_SIZE, corrected
@@ -30,6 +36,8 @@ Extra JSON fields:
 * ``cpu_baseline`` — the CPU oracle (a torch restatement of the reference DGL UDF path, same op
   sequence) on the headline workload, rank 0 at N=1 only, bounded in time; threads = the job's CPU
   share (OMP_NUM_THREADS) or the affinity mask, with the host's counts reported beside it.
+* ``train_step`` — the headline layer's training step; ``graph_build`` — the device graph builder
+  against the host path.
 """
 from __future__ import annotations
 
@@ -56,6 +64,8 @@ from mrp_gnn_amd.dist import GradAllReducer, env_rank_world, shard_graph  # noqa
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 MALL_BYTES = 256 << 20  # Infinity Cache: rotating buffer sets must exceed 2x this
 METRIC = "aggregated node-features/sec (N×C×H×W elems through GCN) at 1/2/4/8 MI355X"
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: a larger output is written as a seeded sample of this size
+DUMP_SEED = 20240  # of the sample's element indices
 
 # BASELINE.json configs[1..4] (configs[0] is the reference's CPU-only case: cpu_baseline).
 # SURVEY.md §8(d) fixes the shapes; "per_gpu" is the graphs one GPU holds in the config.
@@ -353,18 +363,42 @@ def max_over_ranks(seconds, world, device, backend):
     return float(t.item())
 
 
-def timed(fn, steps, world, device, backend):
-    """Barrier + synchronize on both sides of ``steps`` calls; max over ranks (seconds per call)."""
+def timed(fn, steps, world, device, backend, last=None):
+    """Barrier + synchronize on both sides of ``steps`` calls; max over ranks (seconds per call).
+    ``last``: a list that receives what the last call returned."""
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        fn()
+        out = None  # a step's result is released before the next step runs, as when it is discarded
+        out = fn()
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
-    return max_over_ranks((time.perf_counter() - t0) / steps, world, device, backend)
+    seconds = max_over_ranks((time.perf_counter() - t0) / steps, world, device, backend)
+    if last is not None:
+        last[:] = [out]
+    return seconds
+
+
+def dump_outputs(directory, name, out):
+    """``--dump-outputs``: write ``out`` (what the last timed step returned) as
+    ``directory/name.npy`` in float32 — the whole tensor up to ``DUMP_MAX_BYTES``, else the elements
+    at ``DUMP_MAX_BYTES / 4`` flat indices drawn once from a fixed seed (the same indices in every
+    run of the same shape).  Returns the record the result line carries."""
+    os.makedirs(directory, exist_ok=True)
+    flat = out.detach().reshape(-1)
+    n, keep = flat.numel(), DUMP_MAX_BYTES // 4
+    if n > keep:
+        idx = torch.randint(0, n, (keep,), generator=torch.Generator().manual_seed(DUMP_SEED))
+        flat = flat[idx.to(flat.device)]
+    arr = flat.to(torch.float32).cpu().numpy()
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, arr)
+    return {"file": os.path.basename(path), "dtype": "float32", "elements": int(arr.size), "of": n,
+            "shape": list(out.shape), "sample_seed": DUMP_SEED if n > keep else None}
 
 
 def train_step_time(gcn, g, x, world, device, args):
@@ -566,6 +600,13 @@ def parse_args(argv=None):
     ap.add_argument("--nodes", type=int, default=8, help="robots per graph (N)")
     ap.add_argument("--channels", type=int, default=512)
     ap.add_argument("--hw", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: kernel rooflines and copy "
+                         "ceilings, the training step, the BASELINE configs, the graph build and the CPU "
+                         "baseline (--kernel-iters, --cpu-seconds, --no-cpu-baseline, --no-train, "
+                         "--train-steps, --configs and --config-steps only matter with it)")
     ap.add_argument("--kernel-iters", type=int, default=50)
     ap.add_argument("--spinup-s", type=float, default=0.5,
                     help="untimed back-to-back steps before the warmup steps (GPU clock ramp from idle)")
@@ -579,53 +620,14 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def main():
-    args = parse_args()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(sys.argv[1:]))
-
-    rank, world, local = env_rank_world()
-    if args.gpus > 1 and world != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} ranks")
-    ndev = max(torch.cuda.device_count(), 1)
-    device = torch.device("cuda", local % ndev)
-    torch.cuda.set_device(device)
-    if world > 1:
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", device_id=device)
-        else:
-            dist.init_process_group(args.dist_backend)
-
+def full_measurements(result, gcn, g, x, workload, world, rank, device, args):
+    """``--full``: everything the benchmark measures beside the headline figure, added to ``result``
+    in runs of their own after the timed steps."""
     B, N, C, H, W = args.graphs, args.nodes, args.channels, args.hw, args.hw
     P = H * W
-    workload = f"gcn_film_mean_fwd_B{B}_N{N}_complete_C{C}_{H}x{W}_fp32"
-    g = make_workload(B, N, C, H, W, seed=rank, device=device)
-    opt = types.SimpleNamespace(feature_dim=C)
-    torch.manual_seed(0)
-    gcn = mrp.GCN(opt).to(device)
-    x = g.ndata["image"]
     csr = g.csr(device)
     Nt, E = g.num_nodes(), g.num_edges()
-
-    def step():
-        return gcn(g, x)
-
     with torch.no_grad():
-        # Clock / memory power-state ramp: from idle the first ~20-100 ms of back-to-back launches
-        # run up to 1.9x slower (tools/exp_ramp.py: 348 -> 209 -> 188 -> 180 us per aggregation over
-        # the first 60 ms; steps 294 -> 243 -> 226 -> 214 -> 207 us).  Run the step untimed for
-        # --spinup-s seconds first so the K timed steps measure the steady state, not the ramp.
-        spin_t0 = time.perf_counter()
-        spin_steps = 0
-        while time.perf_counter() - spin_t0 < args.spinup_s:
-            for _ in range(20):
-                step()
-            torch.cuda.synchronize(device)
-            spin_steps += 20
-        for _ in range(args.warmup):
-            step()
-        elapsed = timed(step, args.steps, world, device, args.dist_backend) * args.steps
-
         # dominant kernel alone, for the roofline
         z = gcn.edge_encoder.logits(g.edata["pose"])  # what GCN.forward hands the kernel
         out = torch.empty_like(x)
@@ -647,9 +649,82 @@ def main():
     gbuild = graph_build_time(B, N, device)
 
     elems_per_step = Nt * C * P
-    value = world * elems_per_step * args.steps / elapsed
     bytes_launch = alg_bytes_fwd(Nt, E, C, P)
     traffic, traffic_src = pmc_traffic(workload)
+    result["roofline"] = with_ceiling(roofline("film_fwd", bytes_launch, t_kernel, traffic, traffic_src,
+                                               read_frac=(bytes_launch - Nt * C * P * 4) / t_kernel / 1e9 / HBM_PEAK_GBS),
+                                      ceil_h)
+    result["copy_ceiling"] = ceil_h
+    if train is not None:
+        t_train, reducer_buckets = train
+        result["train_step"] = {
+            "what": "GCN layer forward + backward (HIP fused dx/dgamma/dbeta kernel, encoder backward)"
+                    + (" + bucketed gradient all-reduce" if world > 1 else ""),
+            "value": world * elems_per_step / t_train, "unit": "elems/s", "ms_per_step": t_train * 1e3,
+            "allreduce_buckets": reducer_buckets,
+        }
+    if configs:
+        result["configs"] = configs
+    result["graph_build"] = gbuild
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(B, N, C, H, W, args.cpu_seconds)
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse_args(argv)
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(argv))
+
+    rank, world, local = env_rank_world()
+    if args.gpus > 1 and world != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} ranks")
+    ndev = max(torch.cuda.device_count(), 1)
+    device = torch.device("cuda", local % ndev)
+    torch.cuda.set_device(device)
+    if world > 1:
+        if args.dist_backend == "nccl":
+            dist.init_process_group("nccl", device_id=device)
+        else:
+            dist.init_process_group(args.dist_backend)
+
+    B, N, C, H, W = args.graphs, args.nodes, args.channels, args.hw, args.hw
+    P = H * W
+    workload = f"gcn_film_mean_fwd_B{B}_N{N}_complete_C{C}_{H}x{W}_fp32"
+    g = make_workload(B, N, C, H, W, seed=rank, device=device)
+    opt = types.SimpleNamespace(feature_dim=C)
+    torch.manual_seed(0)
+    gcn = mrp.GCN(opt).to(device)
+    x = g.ndata["image"]
+    g.csr(device)
+    Nt = g.num_nodes()
+
+    def step():
+        return gcn(g, x)
+
+    last = []
+    with torch.no_grad():
+        # Clock / memory power-state ramp: from idle the first ~20-100 ms of back-to-back launches
+        # run up to 1.9x slower (tools/exp_ramp.py: 348 -> 209 -> 188 -> 180 us per aggregation over
+        # the first 60 ms; steps 294 -> 243 -> 226 -> 214 -> 207 us).  Run the step untimed for
+        # --spinup-s seconds first so the K timed steps measure the steady state, not the ramp.
+        spin_t0 = time.perf_counter()
+        spin_steps = 0
+        while time.perf_counter() - spin_t0 < args.spinup_s:
+            for _ in range(20):
+                step()
+            torch.cuda.synchronize(device)
+            spin_steps += 20
+        for _ in range(args.warmup):
+            step()
+        elapsed = timed(step, args.steps, world, device, args.dist_backend, last=last) * args.steps
+
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, "gcn_out" if world == 1 else f"gcn_out_rank{rank}", last[0])
+    last.clear()
+
+    value = world * Nt * C * P * args.steps / elapsed
     result = {
         "metric": METRIC,
         "value": value,
@@ -667,24 +742,11 @@ def main():
         "data": "synthetic (seeded complete 8-robot graphs, relative poses from random robot poses, randn features)",
         "config": {"workload": workload, "graphs_per_rank": B, "global_graphs": B * world, "robots": N,
                    "channels": C, "H": H, "W": W, "layers": 1, "parallelism": f"dp{world} (independent graphs)"},
-        "roofline": with_ceiling(roofline("film_fwd", bytes_launch, t_kernel, traffic, traffic_src,
-                                          read_frac=(bytes_launch - Nt * C * P * 4) / t_kernel / 1e9 / HBM_PEAK_GBS),
-                                 ceil_h),
-        "copy_ceiling": ceil_h,
     }
-    if train is not None:
-        t_train, reducer_buckets = train
-        result["train_step"] = {
-            "what": "GCN layer forward + backward (HIP fused dx/dgamma/dbeta kernel, encoder backward)"
-                    + (" + bucketed gradient all-reduce" if world > 1 else ""),
-            "value": world * elems_per_step / t_train, "unit": "elems/s", "ms_per_step": t_train * 1e3,
-            "allreduce_buckets": reducer_buckets,
-        }
-    if configs:
-        result["configs"] = configs
-    result["graph_build"] = gbuild
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(B, N, C, H, W, args.cpu_seconds)
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if args.full:
+        full_measurements(result, gcn, g, x, workload, world, rank, device, args)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$ROOT"
 OUT=gpurun_out/prof_$R
 mkdir -p "$OUT"
-BENCH_ARGS="--steps 20 --warmup 5 --kernel-iters 20 --no-cpu-baseline --configs="
+BENCH_ARGS="--full --steps 20 --warmup 5 --kernel-iters 20 --no-cpu-baseline --configs="
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/bench" -o run --output-format csv \
   -- python3 bench.py $BENCH_ARGS > "$OUT/bench_trace.log" 2>&1
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \

@@ -172,6 +172,9 @@ int mrp_film_mean_bwd(const float* grad_out, int64_t g_node_stride,
  * aggregation scaled by agg_scale, and self_scale * grad_out[u] is added to grad_x[u].  The
  * gradient of x0 is x0_scale * grad_out (an elementwise product the caller forms); x0 and xcopy
  * are not read by the backward.
+ * The typed entry points (mrp_film_mean_fwd_t) read x0 and write xcopy as elements of their `dtype`
+ * (the pointers are declared float* here for the fp32 entry points; cast for the 16-bit types), with the
+ * two node strides in elements of that type.
  */
 typedef struct mrp_agg_epilogue {
     float agg_scale;
@@ -210,6 +213,50 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride,
                          const mrp_agg_epilogue* epilogue,
                          void* workspace, int64_t workspace_bytes,
                          void* stream);
+
+/*
+ * Feature storage types of the typed entry points below.  Feature tensors (x, out, grad_out, grad_x,
+ * grad_x_base, the epilogue's x0 and xcopy) hold elements of `dtype`, and every node stride counts
+ * elements of `dtype`; gb (or its logits) and grad_gb are always fp32.  For the 16-bit types every
+ * loaded element is widened exactly to fp32, the arithmetic is the fp32 kernels' own, operation for
+ * operation, and every stored element is rounded once, to nearest even:
+ *   mrp_film_mean_fwd_t(T, x) == T(mrp_film_mean_fwd_ex(float(x)))        bit for bit,
+ * likewise grad_x for graphs of <= 8 nodes; xcopy receives x's bits unchanged.  Graphs of 9..16 nodes
+ * run film_bwd_dx + the film_bwd_fused Gram pass at 16 bits (no matrix-core / per-edge-slot kernel), so
+ * there grad_x, like grad_gb everywhere, is summed in another order than the fp32 path's.
+ * Slices are 16 bytes (8 elements; forward, <= 8 nodes), 8 bytes (4 elements) or one element, by the
+ * alignment of the pointers, P and the node strides.
+ */
+enum mrp_dtype { MRP_DTYPE_F32 = 0, MRP_DTYPE_BF16 = 1, MRP_DTYPE_F16 = 2 };
+
+/* mrp_film_mean_fwd_ex over a feature storage type.  MRP_DTYPE_F32 is mrp_film_mean_fwd_ex itself; an
+ * unknown dtype returns hipErrorInvalidValue; zero sizes return success without a launch. */
+int mrp_film_mean_fwd_t(int32_t dtype,
+                        const void* x, int64_t x_node_stride,
+                        const float* gb,
+                        const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                        const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                        int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                        int32_t C, int32_t P, int32_t mode,
+                        void* out, int64_t out_node_stride,
+                        const mrp_agg_epilogue* epilogue,
+                        void* stream);
+
+/* mrp_film_mean_bwd_ex (without its reserved workspace) over a feature storage type: grad_out, x,
+ * grad_x and grad_x_base hold `dtype`, grad_gb is fp32. */
+int mrp_film_mean_bwd_t(int32_t dtype,
+                        const void* grad_out, int64_t g_node_stride,
+                        const void* x, int64_t x_node_stride,
+                        const float* gb,
+                        const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                        const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                        int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                        int32_t C, int32_t P, int32_t mode,
+                        void* grad_x, int64_t gx_node_stride,
+                        const void* grad_x_base, int64_t base_node_stride,
+                        float* grad_gb,
+                        const mrp_agg_epilogue* epilogue,
+                        void* stream);
 
 /* Bytes of workspace mrp_film_mean_bwd_ex can use for these graph/feature sizes (0: none needed;
  * always 0 since ABI 12). */
@@ -442,7 +489,9 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * "enc_s1" / "enc_s2" (its two products' split-K counts, 0 = the planner's). */
 int mrp_tuning_set(const char* name, int32_t value);
 
-/* Library identification: ABI version (incremented on signature changes; 21 = this header: v19 plus
+/* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
+ * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature
+ * tensors, enum mrp_dtype); 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

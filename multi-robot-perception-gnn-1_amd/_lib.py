@@ -24,6 +24,8 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_bwd",
     "mrp_film_mean_fwd_ex",
     "mrp_film_mean_bwd_ex",
+    "mrp_film_mean_fwd_t",
+    "mrp_film_mean_bwd_t",
     "mrp_film_mean_bwd_workspace",
     "mrp_compress_fwd",
     "mrp_compress_weight_transpose",
@@ -60,7 +62,7 @@ EXPORTED_SYMBOLS = (
     "mrp_abi_version",
     "mrp_error_string",
 )
-ABI_VERSION = 21
+ABI_VERSION = 22
 MAX_NODES = 16
 
 HIP_ERROR_NOT_SUPPORTED = 801  # hipErrorNotSupported: a fused path declines this shape
@@ -69,6 +71,9 @@ MODE_FILM_MEAN = 0
 MODE_FILM_SUM = 1
 MODE_COPY_MEAN = 2
 GB_LOGITS = 0x100  # mode flag: gb holds pre-sigmoid logits
+DTYPE_F32 = 0  # enum mrp_dtype: the feature storage type of the typed entry points
+DTYPE_BF16 = 1
+DTYPE_F16 = 2
 GRAPH_CSR = 0
 GRAPH_COMPLETE = 1
 
@@ -111,6 +116,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_mean_fwd_ex.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_ex.argtypes = [_P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, ep, _P, _I64, _P]
     lib.mrp_film_mean_bwd_ex.restype = ctypes.c_int
+    lib.mrp_film_mean_fwd_t.argtypes = [_I32, _P, _I64, _P] + graph + [_P, _I64, ep, _P]
+    lib.mrp_film_mean_fwd_t.restype = ctypes.c_int
+    lib.mrp_film_mean_bwd_t.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, ep, _P]
+    lib.mrp_film_mean_bwd_t.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32]
     lib.mrp_film_mean_bwd_workspace.restype = ctypes.c_int64
     lib.mrp_tuning_set.argtypes = [ctypes.c_char_p, _I32]

@@ -12,6 +12,7 @@ Everything here dispatches to the HIP library through its C ABI; a CPU tensor ra
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Optional
 
@@ -25,10 +26,20 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+#: Feature dtypes the kernels read and write natively -> enum mrp_dtype (include/mrp_gnn.h).  16-bit
+#: features are widened exactly on load, the arithmetic is fp32, each output is rounded once at the store.
+FEATURE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+_DTYPE_KEYS = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+
+#: Which kernels ran: ``fwd_f32`` / ``fwd_bf16`` / ``fwd_f16`` and ``bwd_...`` count the launches per
+#: feature dtype (like ``encoder.PATH_COUNTS``); tests use them to assert that the 16-bit kernels ran.
+PATH_COUNTS = collections.Counter()
+
+
 def node_stride(t: torch.Tensor) -> Optional[int]:
-    """Node stride of a (N, C, H, W) fp32 tensor whose per-node C*H*W block is contiguous,
-    else None (then the caller makes it contiguous)."""
-    if t.dim() != 4 or t.dtype != torch.float32:
+    """Node stride (in elements) of a (N, C, H, W) fp32 / bf16 / fp16 tensor whose per-node C*H*W block
+    is contiguous, else None (then the caller makes it contiguous)."""
+    if t.dim() != 4 or t.dtype not in FEATURE_DTYPES:
         return None
     n, c, h, w = t.shape
     if n == 0 or c * h * w == 0:
@@ -72,7 +83,7 @@ def film_mean_cat_forward_into(x: torch.Tensor, gb: Optional[torch.Tensor], csr:
     (``mrp_film_mean_cat_fwd``).  No autograd."""
     C = x.shape[1]
     if cat.dim() != 4 or tuple(cat.shape) != (x.shape[0], 2 * C) + tuple(x.shape[2:]):
-        raise ValueError(f"cat must be {(x.shape[0], 2 * C) + tuple(x.shape[2:])} fp32")
+        raise ValueError(f"cat must be {(x.shape[0], 2 * C) + tuple(x.shape[2:])} in x's dtype")
     return _forward(x, gb, csr, mode, cat[:, C:], epilogue=EpilogueSpec(xcopy=cat[:, :C]))
 
 
@@ -97,8 +108,8 @@ class EpilogueSpec:
         return self.agg_scale == 1.0 and self.self_scale == 0.0 and self.x0 is None and self.xcopy is None
 
 
-def _epilogue_struct(ep: Optional[EpilogueSpec], shape):
-    """(ctypes Epilogue or None, tensors to keep alive)."""
+def _epilogue_struct(ep: Optional[EpilogueSpec], shape, dtype=torch.float32):
+    """(ctypes Epilogue or None, tensors to keep alive); x0 is cast to the features' ``dtype``."""
     if ep is None or ep.is_plain():
         return None, ()
     keep = []
@@ -107,13 +118,13 @@ def _epilogue_struct(ep: Optional[EpilogueSpec], shape):
         if tuple(ep.x0.shape) != tuple(shape):
             raise ValueError(f"x0 must have the node features' shape {tuple(shape)}")
         _require_device(ep.x0)
-        x0, x0s = _as_node_major(ep.x0.float() if ep.x0.dtype != torch.float32 else ep.x0)
+        x0, x0s = _as_node_major(ep.x0.to(dtype) if ep.x0.dtype != dtype else ep.x0)
         keep.append(x0)
         x0p = x0.data_ptr()
     if ep.xcopy is not None:
         xcs = node_stride(ep.xcopy)
-        if xcs is None or tuple(ep.xcopy.shape) != tuple(shape):
-            raise ValueError("xcopy must be (N, C, H, W) fp32 with a contiguous block per node")
+        if xcs is None or tuple(ep.xcopy.shape) != tuple(shape) or ep.xcopy.dtype != dtype:
+            raise ValueError("xcopy must be (N, C, H, W) in x's dtype with a contiguous block per node")
         _require_device(ep.xcopy)
         xcp = ep.xcopy.data_ptr()
     st = _lib.Epilogue(ep.agg_scale, ep.self_scale, x0p, x0s, ep.x0_scale, xcp, xcs)
@@ -125,8 +136,8 @@ def _forward(x, gb, csr, mode, out, epilogue=None):
     n, C, H, W = x.shape
     x, xs = _as_node_major(x)
     os_ = node_stride(out)
-    if os_ is None or tuple(out.shape) != (n, C, H, W):
-        raise ValueError(f"out must be {(n, C, H, W)} fp32 with a contiguous block per node")
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
     if (mode & ~_lib.GB_LOGITS) != _lib.MODE_COPY_MEAN:
         if gb is None:
             raise ValueError("gamma/beta tensor required for FiLM modes")
@@ -138,14 +149,20 @@ def _forward(x, gb, csr, mode, out, epilogue=None):
         gb = None
     if n != csr.num_nodes:
         raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
-    ep, _keep = _epilogue_struct(epilogue, x.shape)
+    ep, _keep = _epilogue_struct(epilogue, x.shape, x.dtype)
     lib = _lib.load_library()
+    graph = (_ptr(gb), _ptr(csr.indptr), _ptr(csr.src), _ptr(csr.eid), _ptr(csr.graph_off),
+             csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes, csr.num_edges, C, H * W, mode)
+    tail = (_ptr(out), os_, ctypes.byref(ep) if ep is not None else None, _stream(x.device))
     with torch.cuda.device(x.device):
-        code = lib.mrp_film_mean_fwd_ex(
-            _ptr(x), xs, _ptr(gb), _ptr(csr.indptr), _ptr(csr.src), _ptr(csr.eid), _ptr(csr.graph_off),
-            csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes, csr.num_edges, C, H * W, mode,
-            _ptr(out), os_, ctypes.byref(ep) if ep is not None else None, _stream(x.device))
-    _lib.check(code, "mrp_film_mean_fwd_ex")
+        if x.dtype == torch.float32:  # the fp32 entry point, as before the typed ones existed
+            what = "mrp_film_mean_fwd_ex"
+            code = lib.mrp_film_mean_fwd_ex(_ptr(x), xs, *graph, *tail)
+        else:
+            what = "mrp_film_mean_fwd_t"
+            code = lib.mrp_film_mean_fwd_t(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *graph, *tail)
+    _lib.check(code, what)
+    PATH_COUNTS["fwd_" + _DTYPE_KEYS[x.dtype]] += 1
     return out
 
 
@@ -157,11 +174,16 @@ def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[tor
     self_scale enter here; the gradient of x0 is x0_scale * grad_out, formed by the caller)."""
     _require_device(grad_out, x)
     n, C, H, W = x.shape
+    dtype = x.dtype  # the feature dtype: grad_out and the base are cast to it, grad_x is allocated in it
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
     grad_out, gs = _as_node_major(grad_out)
     bs = 0
     if grad_x_base is not None:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
         grad_x_base, bs = _as_node_major(grad_x_base)
-    dx = torch.empty((n, C, H, W), device=x.device, dtype=torch.float32) if need_dx else None
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
     dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
     xs = 0
     if need_dgb and (mode & ~_lib.GB_LOGITS) != _lib.MODE_COPY_MEAN:
@@ -180,15 +202,21 @@ def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[tor
         nbytes = int(lib.mrp_film_mean_bwd_workspace(csr.num_graphs, csr.max_nodes, csr.graph_kind, C, H * W))
         if nbytes > 0:
             ws = torch.empty(nbytes // 4 + 1, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        code = lib.mrp_film_mean_bwd_ex(
-            _ptr(grad_out), gs, _ptr(x), xs, _ptr(gb), _ptr(csr.indptr), _ptr(csr.src), _ptr(csr.eid),
+    args = (_ptr(grad_out), gs, _ptr(x), xs, _ptr(gb), _ptr(csr.indptr), _ptr(csr.src), _ptr(csr.eid),
             _ptr(csr.graph_off), csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes, csr.num_edges, C,
             H * W, mode,
             _ptr(dx), (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb),
-            ctypes.byref(ep) if ep is not None else None, _ptr(ws), ws.numel() * 4 if ws is not None else 0,
-            _stream(x.device))
-    _lib.check(code, "mrp_film_mean_bwd_ex")
+            ctypes.byref(ep) if ep is not None else None)
+    with torch.cuda.device(x.device):
+        if dtype == torch.float32:  # the fp32 entry point, as before the typed ones existed
+            what = "mrp_film_mean_bwd_ex"
+            code = lib.mrp_film_mean_bwd_ex(*args, _ptr(ws), ws.numel() * 4 if ws is not None else 0,
+                                            _stream(x.device))
+        else:
+            what = "mrp_film_mean_bwd_t"
+            code = lib.mrp_film_mean_bwd_t(FEATURE_DTYPES[dtype], *args, _stream(x.device))
+    _lib.check(code, what)
+    PATH_COUNTS["bwd_" + _DTYPE_KEYS[dtype]] += 1
     return dx, dgb
 
 
@@ -199,7 +227,7 @@ class FilmMeanFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gb, x0, csr: GraphCSR, mode: int, scales=(1.0, 0.0, 0.0)):
-        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
         ep = EpilogueSpec(scales[0], scales[1], x0, scales[2])
         film_mean_forward_into(x, gb, csr, mode, out, epilogue=ep)
         ctx.save_for_backward(x, gb)
@@ -234,8 +262,8 @@ def _mode_flags(mode, logits: bool) -> int:
 def _check_x(x):
     if x.dim() != 4:
         raise ValueError(f"node features must be (N, C, H, W), got {tuple(x.shape)}")
-    if x.dtype != torch.float32:
-        raise TypeError("node features must be float32 (the reference path is fp32)")
+    if x.dtype not in FEATURE_DTYPES:
+        raise TypeError(f"node features must be float32 (the reference path), bfloat16 or float16, got {x.dtype}")
     _require_device(x)
 
 
@@ -243,7 +271,8 @@ def film_mean(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, mode="
               logits: bool = False) -> torch.Tensor:
     """``mean_e(gamma_e * x_src + beta_e)`` per destination node (see module docstring).
 
-    x: (N, C, H, W) fp32 on a ROCm device; gb: (E, 2C) or (E, C, 2) interleaved gamma/beta
+    x: (N, C, H, W) fp32, bf16 or fp16 on a ROCm device (the output has x's dtype; 16-bit features are
+    widened exactly, aggregated in fp32 and rounded once at the store); gb: (E, 2C) or (E, C, 2) interleaved gamma/beta
     (ignored for ``mode='copy_mean'``), or their pre-sigmoid logits with ``logits=True`` (the
     encoder's Sigmoid then runs inside the kernel); csr: ``RobotGraph.csr(device)``.
     """
@@ -286,7 +315,7 @@ class FilmMeanCatFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gb, csr: GraphCSR, mode: int):
         n, C, H, W = x.shape
-        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=torch.float32)
+        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
         film_mean_cat_forward_into(x, gb, csr, mode, buf)  # the kernel also writes x into buf[:, :C]
         ctx.save_for_backward(x, gb)
         ctx.csr = csr
@@ -309,8 +338,8 @@ class FilmMeanCatFunction(torch.autograd.Function):
 def film_mean_cat(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, mode="film_mean",
                   logits: bool = False) -> torch.Tensor:
     """``torch.cat((x, film_mean(x, gb, csr, mode, logits)), dim=1)`` in one kernel pass."""
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError("node features must be (N, C, H, W) float32")
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
     _require_device(x)
     m = _mode_flags(mode, logits)
     if (m & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN:

@@ -9,14 +9,18 @@ import sys
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG_DIR)
-SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_fwd.hip", "film_mean_bwd.hip", "film_mean_bwd_1_8.hip",
-                                                    "film_mean_bwd_9_12.hip", "film_mean_bwd_13_16.hip",
+# the longest compiles first: the pool starts them in this order
+SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "film_mean_bwd_9_12.hip",
+                                                    "film_mean_bwd_13_16.hip", "film_mean_fwd.hip",
+                                                    "film_mean_bwd_half_1_8.hip", "film_mean_bwd_half_9_12.hip",
+                                                    "film_mean_bwd_half_13_16.hip", "film_mean_fwd_bf16.hip",
+                                                    "film_mean_fwd_f16.hip", "film_mean_bwd.hip",
                                                     "edge_encoder.hip", "frame_graph.hip",
                                                     "compress_gemm.hip", "encoder_split.hip",
                                                     "compress_split.hip")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 HEADERS = [os.path.join(REPO, "include", "mrp_gnn.h")] + [os.path.join(PKG_DIR, "csrc", h) for h in (
-    "film_mean_kernels.hpp", "film_mean_bwd_launch.hpp", "fast_math.hpp", "tuning.hpp", "encoder_split.hpp")]
+    "film_mean_kernels.hpp", "film_mean_bwd_launch.hpp", "film_mean_fwd_launch.hpp", "fast_math.hpp", "tuning.hpp", "encoder_split.hpp")]
 OUT = os.path.join(PKG_DIR, "lib", "libmrp_gnn.so")
 ARCH = os.environ.get("MRP_OFFLOAD_ARCH", "gfx950")
 
@@ -79,7 +83,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             if os.path.exists(obj):
                 os.remove(obj)
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 8)) as ex:
+    workers = min(len(SOURCES), int(os.environ.get("MAX_JOBS", 8)), 16)
+    with ThreadPoolExecutor(max_workers=max(workers, 1)) as ex:
         objs = list(ex.map(lambda s: _compile(s, verbose), SOURCES))
     tmp = OUT + ".tmp"
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", tmp] + objs

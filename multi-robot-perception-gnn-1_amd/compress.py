@@ -467,7 +467,9 @@ class FilmCompressFunction(torch.autograd.Function):
 
 def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
     """Whether :func:`film_compress` takes this layer: fp32 CUDA (N, C, H, W) features and a plain 1x1
-    ``Conv2d(2C, C)`` (the matrix-core kernels, or torch's GEMMs for shapes they decline)."""
+    ``Conv2d(2C, C)`` (the matrix-core kernels, or torch's GEMMs for shapes they decline).  bf16 / fp16
+    features are declined: their layer is the 16-bit cat kernel followed by ``conv(h)``, torch's own
+    convolution (under ``torch.autocast`` with fp32 weights); a native 16-bit compress does not exist."""
     return x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv_is_plain_1x1(conv, x.shape[1])
 
 

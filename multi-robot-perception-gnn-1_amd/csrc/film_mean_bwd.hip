@@ -14,12 +14,25 @@ Geometry regular_geometry(int C, int P, int vec) {
                   : make_geometry(C, P, 1, 2 * tu.bwd_regular_lanes, 2 * tu.bwd_regular_lanes, mrp::kMaxChanPerBlock);
 }
 
-hipError_t dispatch_bwd(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
+hipError_t dispatch_bwd(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
+  if (dtype != MRP_DTYPE_F32) {  // 16-bit features: film_mean_bwd_half_*.hip
+    if (nt >= 1 && nt <= 8) return dispatch_bwd_half_1_8(dtype, nt, complete, a, g, st);
+    if (nt >= 9 && nt <= 12) return dispatch_bwd_half_9_12(dtype, nt, complete, a, g, st);
+    if (nt >= 13 && nt <= 16) return dispatch_bwd_half_13_16(dtype, nt, complete, a, g, st);
+    return hipErrorInvalidValue;
+  }
   if (nt >= 1 && nt <= 8) return dispatch_bwd_1_8(nt, complete, a, g, st);
   if (nt >= 9 && nt <= 12) return dispatch_bwd_9_12(nt, complete, a, g, st);
   if (nt >= 13 && nt <= 16) return dispatch_bwd_13_16(nt, complete, a, g, st);
   return hipErrorInvalidValue;
 }
+
+int film_bwd_impl(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x, int64_t x_node_stride,
+                  const float* gb, const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                  const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                  int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t mode_flags, void* grad_x,
+                  int64_t gx_node_stride, const void* grad_x_base, int64_t base_node_stride, float* grad_gb,
+                  const mrp_agg_epilogue* ep, void* stream);
 
 }  // namespace
 
@@ -48,6 +61,38 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride, const flo
                          float* grad_x, int64_t gx_node_stride, const float* grad_x_base, int64_t base_node_stride,
                          float* grad_gb, const mrp_agg_epilogue* ep, void* workspace, int64_t workspace_bytes,
                          void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  return film_bwd_impl(MRP_DTYPE_F32, grad_out, g_node_stride, x, x_node_stride, gb, indptr, src, eid, graph_off,
+                       num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P, mode_flags, grad_x,
+                       gx_node_stride, grad_x_base, base_node_stride, grad_gb, ep, stream);
+}
+
+int mrp_film_mean_bwd_t(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x,
+                        int64_t x_node_stride, const float* gb, const int32_t* indptr, const int32_t* src,
+                        const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                        int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
+                        int32_t mode_flags, void* grad_x, int64_t gx_node_stride, const void* grad_x_base,
+                        int64_t base_node_stride, float* grad_gb, const mrp_agg_epilogue* ep, void* stream) {
+  if (dtype != MRP_DTYPE_F32 && dtype != MRP_DTYPE_BF16 && dtype != MRP_DTYPE_F16) return hipErrorInvalidValue;
+  return film_bwd_impl(dtype, grad_out, g_node_stride, x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs,
+                       max_nodes, graph_kind, num_nodes, num_edges, C, P, mode_flags, grad_x, gx_node_stride,
+                       grad_x_base, base_node_stride, grad_gb, ep, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The backward behind mrp_film_mean_bwd{,_ex,_t}.  grad_out, x, grad_x and grad_x_base hold elements of
+// `dtype` (strides in elements); gb and grad_gb are fp32.
+int film_bwd_impl(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x, int64_t x_node_stride,
+                  const float* gb, const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                  const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                  int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t mode_flags, void* grad_x,
+                  int64_t gx_node_stride, const void* grad_x_base, int64_t base_node_stride, float* grad_gb,
+                  const mrp_agg_epilogue* ep, void* stream) {
+  const bool half = dtype != MRP_DTYPE_F32;  // 16-bit features
   const float agg_scale = ep != nullptr ? ep->agg_scale : 1.f;
   const float self_scale = ep != nullptr ? ep->self_scale : 0.f;
   const int32_t logits = (mode_flags & MRP_AGG_GB_LOGITS) ? 1 : 0;
@@ -72,17 +117,19 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride, const flo
   if (want_dx && grad_x_base != nullptr && base_node_stride < plane) return hipErrorInvalidValue;
   if (want_dgb && (x == nullptr || x_node_stride < plane)) return hipErrorInvalidValue;
   if (!copy && num_edges > 0 && gb == nullptr) return hipErrorInvalidValue;
-  bool vec4 = (P % 4 == 0) && (g_node_stride % 4 == 0) && aligned16(grad_out);
-  if (want_dx) vec4 = vec4 && (gx_node_stride % 4 == 0) && aligned16(grad_x);
-  if (want_dx && grad_x_base) vec4 = vec4 && (base_node_stride % 4 == 0) && aligned16(grad_x_base);
-  if (want_dgb) vec4 = vec4 && (x_node_stride % 4 == 0) && aligned16(x);
+  // 4-element slices: 16 bytes of fp32, 8 bytes of a 16-bit type
+  auto slice_aligned = [half](const void* p) { return half ? aligned8(p) : aligned16(p); };
+  bool vec4 = (P % 4 == 0) && (g_node_stride % 4 == 0) && slice_aligned(grad_out);
+  if (want_dx) vec4 = vec4 && (gx_node_stride % 4 == 0) && slice_aligned(grad_x);
+  if (want_dx && grad_x_base) vec4 = vec4 && (base_node_stride % 4 == 0) && slice_aligned(grad_x_base);
+  if (want_dgb) vec4 = vec4 && (x_node_stride % 4 == 0) && slice_aligned(x);
   // 16-byte slices: with the DPP lane reduction they beat 8-byte slices (310 vs 322 us at B=32,
   // N=8, C=512, 32x32) despite 2 waves/SIMD instead of 3.  VEC=2 stays compiled for experiments.
   int vec = vec4 ? 4 : 1;
   Geometry g;
   const int kdeg = MRP_GRAPH_IS_REGULAR(graph_kind) ? MRP_GRAPH_REGULAR_K(graph_kind) : 0;
-  if (max_nodes > 8 && kdeg >= 1 && kdeg <= 8) {
-    // film_bwd_regular: 8-byte slices on 16 lanes per plane (367 us against 569 us on 64 lanes at
+  if (!half && max_nodes > 8 && kdeg >= 1 && kdeg <= 8) {
+    // film_bwd_regular (fp32 features only; 16-bit ones take film_bwd_dx + the Gram pass below): 8-byte slices on 16 lanes per plane (367 us against 569 us on 64 lanes at
     // k-NN(4) N=16 C=1024 16x16): its prologue and lane reduction are amortised over more slices
     const Tuning& tu = tuning();
     vec = (vec4 && kdeg <= 4 && tu.bwd_regular_vec == 2) ? 2 : 1;
@@ -95,13 +142,11 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride, const flo
   } else {
     g = make_geometry(C, P, vec, 64, 64, mrp::kMaxChanPerBlock);  // film_bwd_dx + Gram pass
   }
-  (void)workspace;
-  (void)workspace_bytes;
-  // film_bwd_mfma: regular graphs of 9..16 nodes and complete graphs, whole pixel groups of 64
+  // film_bwd_mfma (fp32 features only): regular graphs of 9..16 nodes and complete graphs, whole pixel groups of 64
   const bool complete = graph_kind == MRP_GRAPH_COMPLETE;
   const bool mfma_kind = (max_nodes > 8 && kdeg >= 1 && kdeg <= 8 && tuning().bwd_regular_mfma) ||
                          (complete && max_nodes > 8 && tuning().bwd_complete_mfma);
-  if (mfma_kind && vec4 && P % 64 == 0) {
+  if (!half && mfma_kind && vec4 && P % 64 == 0) {
     // per-lane row offsets are 32-bit: 15 node strides + two planes (a block's channel pair)
     const int64_t lim = (int64_t)1 << 32;
     const int64_t span = (int64_t)plane * 4 + (int64_t)P * 4;
@@ -152,8 +197,8 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride, const flo
   a.epi = (agg_scale != 1.f || self_scale != 0.f) ? 1 : 0;
   a.psplit = 1;
   a.nmax = max_nodes;
-  return dispatch_bwd(max_nodes, graph_kind == MRP_GRAPH_COMPLETE, a, g, st);
+  return dispatch_bwd(dtype, max_nodes, graph_kind == MRP_GRAPH_COMPLETE, a, g, st);
 }
 
-}  // extern "C"
+}  // namespace
 

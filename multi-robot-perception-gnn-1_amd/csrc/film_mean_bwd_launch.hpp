@@ -52,6 +52,58 @@ hipError_t launch_bwd_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st
   }
 }
 
+// 16-bit features (T = mrp::bf16_t / mrp::f16_t): film_bwd_fused up to 8 nodes, film_bwd_dx + the VB = 4
+// Gram pass beyond (no matrix-core or per-edge-slot kernel), slices of 4 elements (8 bytes) or 1, and no
+// PRE2 variant: half of the fp32 instantiation set per dtype (1..8 nodes: 64 kernels against 128).
+template <typename T, int NT, bool COMPLETE, bool DXB>
+hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st) {
+  if constexpr (NT <= 8) {
+    const AggArgs& a = a_in;
+    const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits, g.lpc);
+    if (g.vec == 4)
+      MRP_LAUNCH((mrp::film_bwd_fused<NT, NT, 4, COMPLETE, DXB, 1, false, T>), lds);
+    else
+      MRP_LAUNCH((mrp::film_bwd_fused<NT, NT, 1, COMPLETE, DXB, 1, false, T>), lds);
+    return hipGetLastError();
+  } else {
+    if (a_in.want_dx) {
+      const AggArgs& a = a_in;
+      const size_t lds = lds_dx<NT>(g.cpb);
+      if (g.vec == 4)
+        MRP_LAUNCH((mrp::film_bwd_dx<NT, 4, COMPLETE, DXB, T>), lds);
+      else
+        MRP_LAUNCH((mrp::film_bwd_dx<NT, 1, COMPLETE, DXB, T>), lds);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    if (a_in.want_dgb) {
+      AggArgs a = a_in;
+      a.want_dx = 0;
+      const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits);
+      if (g.vec == 4)
+        MRP_LAUNCH((mrp::film_bwd_fused<NT, 4, 4, COMPLETE, false, 1, false, T>), lds);
+      else
+        MRP_LAUNCH((mrp::film_bwd_fused<NT, 4, 1, COMPLETE, false, 1, false, T>), lds);
+      return hipGetLastError();
+    }
+    return hipSuccess;
+  }
+}
+
+template <typename T, int NT>
+hipError_t launch_bwd_half_nt(bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
+  if (g.vec != 4 && g.vec != 1) return hipErrorInvalidValue;
+  if (complete)
+    return a.dxb ? launch_bwd_half_ntb<T, NT, true, true>(a, g, st) : launch_bwd_half_ntb<T, NT, true, false>(a, g, st);
+  return a.dxb ? launch_bwd_half_ntb<T, NT, false, true>(a, g, st) : launch_bwd_half_ntb<T, NT, false, false>(a, g, st);
+}
+
+// One case of a 16-bit dispatch switch over the graph size.
+#define MRP_HALF_NT_CASE(N)                                                                            \
+  case N:                                                                                              \
+    return dtype == MRP_DTYPE_BF16 ? launch_bwd_half_nt<mrp::bf16_t, N>(complete, a, g, st)            \
+                                   : launch_bwd_half_nt<mrp::f16_t, N>(complete, a, g, st);
+
 template <int NT, int KMAX, bool DXB>
 hipError_t launch_bwd_regular(const AggArgs& a, const Geometry& g, hipStream_t st) {
   // VEC 4 would need 4*NT registers more per operand and spills; KMAX 8 only fits at VEC 1

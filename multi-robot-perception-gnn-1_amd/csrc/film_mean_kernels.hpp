@@ -48,20 +48,22 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int kBlock = 256;  // threads per workgroup (4 waves)
 constexpr int kMaxChanPerBlock = 16;
 
+// Feature tensors (x, g, out, dxb, xc, x0) are typeless here: a kernel reads them as its storage type T
+// (float, __bf16 or _Float16; strides in elements of T).  gamma/beta and their gradient are always fp32.
 struct AggArgs {
-  const float* x;  // source node features (fwd: x, bwd: x)
+  const void* x;  // source node features (fwd: x, bwd: x)
   int64_t xs;      // node stride (elements)
-  const float* g;  // bwd: grad_out
+  const void* g;  // bwd: grad_out
   int64_t gs;
   const float* gb;  // (E, C, 2) interleaved gamma/beta
   const int32_t* indptr;
   const int32_t* src;
   const int32_t* eid;
   const int32_t* goff;
-  float* out;  // fwd: out, bwd: grad_x
+  void* out;  // fwd: out, bwd: grad_x
   int64_t os;
   float* dgb;  // bwd: grad of gb (E, C, 2)
-  const float* dxb;  // bwd: optional grad_x base (added to grad_x), node stride dxbs
+  const void* dxb;  // bwd: optional grad_x base (added to grad_x), node stride dxbs
   int64_t dxbs;
   int32_t C, P, PV, mode;
   int32_t lpc;  // lanes per channel plane (power of two <= 64; <= 256 in film_bwd_fused: lpc/64 waves)
@@ -70,7 +72,7 @@ struct AggArgs {
   int32_t want_dx, want_dgb;
   int32_t logits;  // gb holds pre-sigmoid logits (MRP_AGG_GB_LOGITS): apply sigmoid on load
   int32_t kdeg;    // MRP_GRAPH_REGULAR: every node's in-degree (else 0)
-  float* xc;       // forward: optional copy of x (the first half of a concatenation buffer)
+  void* xc;       // forward: optional copy of x (the first half of a concatenation buffer)
   int64_t xcs;     // its node stride
   int32_t psplit;  // forward: plane segments per (graph, channel block) (0 or 1: whole plane)
   // epilogue (mrp_agg_epilogue): forward out = agg_scale*a + self_scale*x[v] + x0_scale*x0[v];
@@ -78,13 +80,77 @@ struct AggArgs {
   // and self_scale*grad_out[u] is added to grad_x[u].  epi = 0: plain (agg_scale 1, the rest 0).
   int32_t epi;
   float agg_scale, self_scale, x0_scale;
-  const float* x0;
+  const void* x0;
   int64_t x0s;
   int32_t nmax;  // max_nodes (COMPLETE graphs: every graph's node count)
 };
 
-// Forward epilogue of destination `node`, channel c, slice at `off` (see AggArgs::epi).
+// Storage types of the feature tensors.  16-bit elements are widened exactly to fp32 on load and
+// rounded once (to nearest even) at the store; all arithmetic in between is the fp32 kernels' own.
+typedef __bf16 bf16_t;
+typedef _Float16 f16_t;
+
 template <int VEC>
+struct Frag {
+  float v[VEC];
+};
+
+// A slice of VEC elements of T as one (nontemporal: streamed once) access of VEC * sizeof(T) bytes.
+// float: 16 / 8 / 4 bytes for VEC 4 / 2 / 1; 16-bit: 16 / 8 / 4 / 2 bytes for VEC 8 / 4 / 2 / 1.
+template <int VEC, bool NTL, typename T>
+__device__ __forceinline__ Frag<VEC> load_frag16(const T* p) {
+  static_assert(sizeof(T) == 2, "16-bit storage");
+  Frag<VEC> f;
+  if constexpr (VEC == 1) {
+    f.v[0] = (float)(NTL ? __builtin_nontemporal_load(p) : *p);
+  } else {
+    typedef T tv __attribute__((ext_vector_type(VEC)));
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    const tv* q = reinterpret_cast<const tv*>(p);
+    const tv t = NTL ? __builtin_nontemporal_load(q) : *q;
+    const fv w = __builtin_convertvector(t, fv);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) f.v[k] = w[k];
+  }
+  return f;
+}
+
+template <int VEC, bool NTL, typename T>
+__device__ __forceinline__ void store_frag16(T* p, const Frag<VEC>& f) {
+  static_assert(sizeof(T) == 2, "16-bit storage");
+  if constexpr (VEC == 1) {
+    const T t = (T)f.v[0];
+    if (NTL)
+      __builtin_nontemporal_store(t, p);
+    else
+      *p = t;
+  } else {
+    typedef T tv __attribute__((ext_vector_type(VEC)));
+    typedef float fv __attribute__((ext_vector_type(VEC)));
+    fv w;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) w[k] = f.v[k];
+    const tv t = __builtin_convertvector(w, tv);
+    if (NTL)
+      __builtin_nontemporal_store(t, reinterpret_cast<tv*>(p));
+    else
+      *reinterpret_cast<tv*>(p) = t;
+  }
+}
+
+template <int VEC, bool NTL>
+__device__ __forceinline__ Frag<VEC> load_frag(const float* p);
+template <int VEC, bool NTL>
+__device__ __forceinline__ Frag<VEC> load_frag(const bf16_t* p) {
+  return load_frag16<VEC, NTL>(p);
+}
+template <int VEC, bool NTL>
+__device__ __forceinline__ Frag<VEC> load_frag(const f16_t* p) {
+  return load_frag16<VEC, NTL>(p);
+}
+
+// Forward epilogue of destination `node`, channel c, slice at `off` (see AggArgs::epi).
+template <int VEC, typename T>
 __device__ __forceinline__ void apply_epilogue(const AggArgs& a, float* acc, const float* xself, int node, int c,
                                                int64_t off) {
   if (a.agg_scale != 1.f) {
@@ -96,9 +162,13 @@ __device__ __forceinline__ void apply_epilogue(const AggArgs& a, float* acc, con
     for (int k = 0; k < VEC; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(a.self_scale, xself[k]));
   }
   if (a.x0 != nullptr) {
-    const float* p = a.x0 + (int64_t)node * a.x0s + (int64_t)c * a.P + off;
+    const T* p = static_cast<const T*>(a.x0) + (int64_t)node * a.x0s + (int64_t)c * a.P + off;
     float z[VEC];
-    if constexpr (VEC == 4) {
+    if constexpr (!std::is_same<T, float>::value) {
+      const Frag<VEC> t = load_frag<VEC, true>(p);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) z[k] = t.v[k];
+    } else if constexpr (VEC == 4) {
       const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
       z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
     } else if constexpr (VEC == 2) {
@@ -119,11 +189,6 @@ __device__ __forceinline__ float2 sigmoid_backward(float2 grad, float2 z) {
   const float sg = sigmoidf(z.x), sb = sigmoidf(z.y);
   return make_float2(grad.x * sg * (1.f - sg), grad.y * sb * (1.f - sb));
 }
-
-template <int VEC>
-struct Frag {
-  float v[VEC];
-};
 
 template <int VEC, bool NTL>
 __device__ __forceinline__ Frag<VEC> load_frag(const float* p) {
@@ -174,14 +239,25 @@ __device__ __forceinline__ void store_frag(float* p, const Frag<VEC>& f) {
   }
 }
 
+template <int VEC, bool NTL>
+__device__ __forceinline__ void store_frag(bf16_t* p, const Frag<VEC>& f) {
+  store_frag16<VEC, NTL>(p, f);
+}
+template <int VEC, bool NTL>
+__device__ __forceinline__ void store_frag(f16_t* p, const Frag<VEC>& f) {
+  store_frag16<VEC, NTL>(p, f);
+}
+
 // Wave-uniform base + 32-bit lane byte offset: lets the compiler use the SGPR-base form of
 // global_load/store (saddr + 32-bit vaddr) instead of a 64-bit VGPR address per access — with N
 // source and N destination planes per slice those addresses are most of a kernel's VGPRs.
-__device__ __forceinline__ const float* at_bytes(const float* base, uint32_t off) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off);
+template <typename T>
+__device__ __forceinline__ const T* at_bytes(const T* base, uint32_t off) {
+  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
 }
-__device__ __forceinline__ float* at_bytes(float* base, uint32_t off) {
-  return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off);
+template <typename T>
+__device__ __forceinline__ T* at_bytes(T* base, uint32_t off) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off);
 }
 
 template <int NT>
@@ -435,7 +511,8 @@ __device__ __forceinline__ void complete_rest(const AggArgs& a, int64_t ebase, i
 // MODE >= 0: the FiLM mode as a compile-time constant (the hot path: COMPLETE, MRP_AGG_FILM_MEAN,
 // N <= 8): no per-term select between the modes, and the mean's division by N - 1 as the exact
 // three-instruction quotient (fast_math.hpp) for a whole slice at once.  MODE = -1: mode at run time.
-template <int NT, int VEC, bool COMPLETE, int MODE = -1>
+// T: the feature tensors' storage type (float, bf16_t, f16_t); VEC counts elements of T.
+template <int NT, int VEC, bool COMPLETE, int MODE = -1, typename T = float>
 __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
   constexpr int SZ = Tile<NT>::SZ;
   constexpr int NTP = Tile<NT>::NTP;
@@ -469,9 +546,9 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const float* xb = a.x + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
-  float* ob = a.out + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
-  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * 4u;
+  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
+  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
 
   // prologue part 1 (COMPLETE): gamma/beta into registers
   float2 reg[CompleteSlots<NT>::kPer];
@@ -488,7 +565,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       const int uu = u < n ? u : n - 1;  // clamp (ragged batch); never used for output
-      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * 4u));
+      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * (uint32_t)sizeof(T)));
 #pragma unroll
       for (int k = 0; k < VEC; ++k) xv[k][u] = f.v[k];
     }
@@ -519,7 +596,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
 
   while (j < jend) {
     const int64_t off = (int64_t)j * VEC;
-    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * 4u;
+    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * (uint32_t)sizeof(T);
     // Re-read the tiles from LDS every slice: laundering the tile offset stops the compiler from
     // hoisting all N*N weights into registers (which would cost occupancy or spill).
     int tile = grp * SZ;
@@ -590,7 +667,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
             float xself[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) xself[k] = xv[k][v0 + i];
-            apply_epilogue<VEC>(a, accs[i].v, xself, node0 + v0 + i, c, off);
+            apply_epilogue<VEC, T>(a, accs[i].v, xself, node0 + v0 + i, c, off);
           }
           store_frag<VEC, true>(at_bytes(ob + (int64_t)(v0 + i) * a.os, lane_off), accs[i]);
         }
@@ -609,7 +686,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
         float xself[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) xself[k] = xv[k][v];
-        apply_epilogue<VEC>(a, acc.v, xself, node0 + v, c, off);
+        apply_epilogue<VEC, T>(a, acc.v, xself, node0 + v, c, off);
       }
       store_frag<VEC, true>(at_bytes(ob + (int64_t)v * a.os, lane_off), acc);
     }
@@ -617,7 +694,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
     if (a.xc != nullptr) {
       // cat((x, aggregate), 1): the slices of x are in registers already; writing them here saves
       // the separate copy's read of x
-      float* xcb = a.xc + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
+      T* xcb = static_cast<T*>(a.xc) + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
         if (u >= n) break;
@@ -649,7 +726,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
 // the mode is a mean: the slot loop has no exit test and the mean's division is the exact product
 // by 1/KC (x * 2^-k is the correctly rounded x / 2^k), instead of the ~10-instruction IEEE division
 // per destination and element.  KC = 0: runtime K and mode.
-template <int NT, int KMAX, int VEC, int KC = 0>
+template <int NT, int KMAX, int VEC, int KC = 0, typename T = float>
 __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
   static_assert(KC == 0 || (KC <= KMAX && (KC & (KC - 1)) == 0), "compile-time degree: a power of two");
   constexpr int NS = NT * KMAX;
@@ -679,9 +756,9 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const float* xb = a.x + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
-  float* ob = a.out + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
-  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * 4u;
+  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
+  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
 
   // First slice's loads, issued before the prologue's two dependent rounds.  Element k of every
   // source's slice lives in one NT-wide vector value, so the wave-uniform source index is a dynamic
@@ -693,7 +770,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       const int uu = u < n ? u : n - 1;
-      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * 4u));
+      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * (uint32_t)sizeof(T)));
 #pragma unroll
       for (int k = 0; k < VEC; ++k) xs[k][u] = f.v[k];
     }
@@ -784,7 +861,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
   const float d = (float)K;
   while (j < jend) {
     const int64_t off = (int64_t)j * VEC;
-    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * 4u;
+    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * (uint32_t)sizeof(T);
     // every destination row is computed (full unroll); rows past the graph's nodes are not stored
 #pragma unroll
     for (int v = 0; v < NT; ++v) {
@@ -817,7 +894,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
         float xself[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) xself[k] = xs[k][v];
-        apply_epilogue<VEC>(a, acc, xself, node0 + v, c, off);
+        apply_epilogue<VEC, T>(a, acc, xself, node0 + v, c, off);
       }
       if (v < n) {
         Frag<VEC> o;
@@ -827,7 +904,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
       }
     }
     if (a.xc != nullptr) {
-      float* xcb = a.xc + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
+      T* xcb = static_cast<T*>(a.xc) + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
         if (u >= n) break;
@@ -846,7 +923,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
 // Backward, grad_x only (used for NT > 8, where the fused kernel's Gram accumulators would not
 // fit in registers):  grad_x[u] = sum_v Wt[u][v] * G[v].
 // ---------------------------------------------------------------------------
-template <int NT, int VEC, bool COMPLETE, bool DXB>
+template <int NT, int VEC, bool COMPLETE, bool DXB, typename T = float>
 __global__ void __launch_bounds__(kBlock) film_bwd_dx(AggArgs a) {
   constexpr int SZ = Tile<NT>::SZ;
   constexpr int NTP = Tile<NT>::NTP;
@@ -878,14 +955,14 @@ __global__ void __launch_bounds__(kBlock) film_bwd_dx(AggArgs a) {
   if (grp >= a.cpb || c >= a.C) return;
 
   // uniform bases, per-lane 32-bit byte offsets (at_bytes); slices as NT-wide vectors (no scratch)
-  const float* gbase = a.g + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
-  float* ob = a.out + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
-  const float* dxbase = a.dxb != nullptr ? a.dxb + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
-  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * 4u;
+  const T* gbase = static_cast<const T*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
+  T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
+  const T* dxbase = a.dxb != nullptr ? static_cast<const T*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
+  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
   typedef float vnt __attribute__((ext_vector_type(NT <= 4 ? 4 : (NT <= 8 ? 8 : 16))));
 
   for (int j = li; j < a.PV; j += a.lpc) {
-    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * 4u;
+    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * (uint32_t)sizeof(T);
     int tile = grp * SZ;  // laundered: keep the weights in LDS, not hoisted into registers
     asm volatile("" : "+v"(tile));
     const float* W = Wt + tile;
@@ -1034,7 +1111,8 @@ __device__ __forceinline__ void with_lanes(int lpc, F&& f) {
 // the prologue, into two register sets, so the second slice's loads are in flight while the first
 // is reduced instead of being issued after it.  At N = 8 the kernel runs 2 waves per SIMD either
 // way (192 VGPRs with one set), so the second set costs no occupancy.
-template <int NT, int VB, int VEC, bool COMPLETE, bool DXB = false, int MINW = 1, bool PRE2 = false>
+template <int NT, int VB, int VEC, bool COMPLETE, bool DXB = false, int MINW = 1, bool PRE2 = false,
+          typename T = float>
 __global__ void __launch_bounds__(kBlock, MINW) film_bwd_fused(AggArgs a) {
   constexpr int SZ = Tile<NT>::SZ;
   constexpr int NTP = Tile<NT>::NTP;
@@ -1067,11 +1145,11 @@ __global__ void __launch_bounds__(kBlock, MINW) film_bwd_fused(AggArgs a) {
   const bool active = grp < a.cpb && c < a.C;
 
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const float* gbase = a.g + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
-  const float* xbase = a.x + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
-  float* ob = a.out + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
-  const float* dxbase = a.dxb != nullptr ? a.dxb + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
-  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * 4u;
+  const T* gbase = static_cast<const T*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
+  const T* xbase = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
+  const T* dxbase = a.dxb != nullptr ? static_cast<const T*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
+  const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
   const bool do_dx = kOnePass && a.want_dx;
 
   // slice fragments: for the one-pass kernel the first slice is loaded before the prologue, so the
@@ -1081,7 +1159,7 @@ __global__ void __launch_bounds__(kBlock, MINW) film_bwd_fused(AggArgs a) {
   Frag<VEC> gv2[PRE2 ? VB : 1];
   Frag<VEC> xv2[PRE2 ? NT : 1];
   auto load_into = [&](Frag<VEC>* G, Frag<VEC>* X, int vb, int j) {
-    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * 4u;
+    const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * (uint32_t)sizeof(T);
 #pragma unroll
     for (int i = 0; i < VB; ++i) {
       const int v = vb + i;
@@ -1092,7 +1170,7 @@ __global__ void __launch_bounds__(kBlock, MINW) film_bwd_fused(AggArgs a) {
     // rows, unused.  Under `if (a.want_dgb)` the branch's join made hipcc copy the landed registers into
     // place at its end — an s_waitcnt vmcnt(0) between this slice's loads and the next's, so PRE2's second
     // slice set was only requested after the first had arrived (two dependent memory round trips)
-    const float* xb = a.want_dgb ? xbase : gbase;
+    const T* xb = a.want_dgb ? xbase : gbase;
     const int64_t xstride = a.want_dgb ? a.xs : a.gs;
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
@@ -1128,7 +1206,7 @@ __global__ void __launch_bounds__(kBlock, MINW) film_bwd_fused(AggArgs a) {
       int j = li;
       if (!kOnePass && j < a.PV) load_slice(vb, j);
       while (j < a.PV) {
-        const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * 4u;
+        const uint32_t lane_off = lane_plane + (uint32_t)j * VEC * (uint32_t)sizeof(T);
         int tile = grp * SZ;  // laundered: keep the weights in LDS, not hoisted into registers
         asm volatile("" : "+v"(tile));
         const float* W = Wt + tile;
@@ -1353,10 +1431,10 @@ __global__ void __launch_bounds__(kBlock) film_bwd_regular(AggArgs a) {
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const float* gbase = a.g + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
-  const float* xbase = a.x + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
-  float* ob = a.out + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
-  const float* dxbase = a.dxb != nullptr ? a.dxb + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
+  const float* gbase = static_cast<const float*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c0 * a.P;
+  const float* xbase = static_cast<const float*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  float* ob = static_cast<float*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
+  const float* dxbase = a.dxb != nullptr ? static_cast<const float*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P : nullptr;
   const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * 4u;
 
 
@@ -1695,7 +1773,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   auto load_step = [&](int st, mf4 (&gr)[4], mf4 (&xr)[4], mf4 (&br)[DXB ? 4 : 1]) {
     const int i = st / ngroups, g = st - i * ngroups;
     const int c = blk_c(i);
-    const float* gbase = a.g + (int64_t)node0 * a.gs + (int64_t)c * a.P;
+    const float* gbase = static_cast<const float*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c * a.P;
     const bool h1 = CB == 1 || hvalid(i, 1);
 #pragma unroll
     for (int bb = 0; bb < 4; ++bb) {
@@ -1704,7 +1782,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     }
     if constexpr (DXB) {
       if (a.want_dx) {
-        const float* dxbase = a.dxb + (int64_t)node0 * a.dxbs + (int64_t)c * a.P;
+        const float* dxbase = static_cast<const float*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c * a.P;
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) {
           const uint32_t off = boff4[bb] - (h1 ? 0u : (uint32_t)hq[bb] * (uint32_t)a.P * 4u);
@@ -1713,7 +1791,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
       }
     }
     if (a.want_dgb) {
-      const float* xbase = a.x + (int64_t)node0 * a.xs + (int64_t)c * a.P;
+      const float* xbase = static_cast<const float*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c * a.P;
       const uint32_t xo = (uint32_t)min(nx, n - 1) * (uint32_t)a.xs * 4u + (uint32_t)(h1 ? hx : 0) * (uint32_t)a.P * 4u +
                           (uint32_t)q * 16u;
 #pragma unroll
@@ -1731,7 +1809,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     // (copy mode: gb may be null, so grad_out's first element is read and discarded instead)
     float graw[NE];
     const bool copy = a.mode == MRP_AGG_COPY_MEAN || a.gb == nullptr;
-    const float* gsrc = copy ? a.g : a.gb;
+    const float* gsrc = copy ? static_cast<const float*>(a.g) : a.gb;
 #pragma unroll
     for (int jj = 0; jj < NE; ++jj)
       graw[jj] = gsrc[copy ? 0 : ((es[jj] >= 0 ? es[jj] : 0) * a.C + c0 + pcl) * 2];
@@ -1788,7 +1866,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     for (int bb = 0; bb < 4; ++bb)
       if (!rvalid[bb]) gr[bb] = mf4{0.f, 0.f, 0.f, 0.f};
     if (a.want_dx) {
-      float* obase = a.out + (int64_t)node0 * a.os + (int64_t)c * a.P;
+      float* obase = static_cast<float*>(a.out) + (int64_t)node0 * a.os + (int64_t)c * a.P;
       mf4 acc[4];
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc) {
@@ -1961,28 +2039,6 @@ size_t lds_bwd(int cpb, bool complete_logits, int lpc = 64) {
 #define MRP_LAUNCH(KERNEL, LDS) hipLaunchKernelGGL((KERNEL), dim3((unsigned)g.grid), dim3(g.threads), (LDS), st, a)
 
 
-#define MRP_DISPATCH_NT(NTV, COMPLETE, FN, ...)                                        \
-  switch (NTV) {                                                                       \
-    case 1: return COMPLETE ? FN<1, true>(__VA_ARGS__) : FN<1, false>(__VA_ARGS__);    \
-    case 2: return COMPLETE ? FN<2, true>(__VA_ARGS__) : FN<2, false>(__VA_ARGS__);    \
-    case 3: return COMPLETE ? FN<3, true>(__VA_ARGS__) : FN<3, false>(__VA_ARGS__);    \
-    case 4: return COMPLETE ? FN<4, true>(__VA_ARGS__) : FN<4, false>(__VA_ARGS__);    \
-    case 5: return COMPLETE ? FN<5, true>(__VA_ARGS__) : FN<5, false>(__VA_ARGS__);    \
-    case 6: return COMPLETE ? FN<6, true>(__VA_ARGS__) : FN<6, false>(__VA_ARGS__);    \
-    case 7: return COMPLETE ? FN<7, true>(__VA_ARGS__) : FN<7, false>(__VA_ARGS__);    \
-    case 8: return COMPLETE ? FN<8, true>(__VA_ARGS__) : FN<8, false>(__VA_ARGS__);    \
-    case 9: return COMPLETE ? FN<9, true>(__VA_ARGS__) : FN<9, false>(__VA_ARGS__);    \
-    case 10: return COMPLETE ? FN<10, true>(__VA_ARGS__) : FN<10, false>(__VA_ARGS__); \
-    case 11: return COMPLETE ? FN<11, true>(__VA_ARGS__) : FN<11, false>(__VA_ARGS__); \
-    case 12: return COMPLETE ? FN<12, true>(__VA_ARGS__) : FN<12, false>(__VA_ARGS__); \
-    case 13: return COMPLETE ? FN<13, true>(__VA_ARGS__) : FN<13, false>(__VA_ARGS__); \
-    case 14: return COMPLETE ? FN<14, true>(__VA_ARGS__) : FN<14, false>(__VA_ARGS__); \
-    case 15: return COMPLETE ? FN<15, true>(__VA_ARGS__) : FN<15, false>(__VA_ARGS__); \
-    case 16: return COMPLETE ? FN<16, true>(__VA_ARGS__) : FN<16, false>(__VA_ARGS__); \
-    default: return hipErrorInvalidValue;                                              \
-  }
-
-
 inline bool common_args_ok(const int32_t* indptr, const int32_t* src, const int32_t* eid, const int32_t* graph_off,
                     int32_t num_graphs, int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
                     int32_t C, int32_t P, int32_t mode) {
@@ -2018,5 +2074,9 @@ namespace mrp_host {
 hipError_t dispatch_bwd_1_8(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 hipError_t dispatch_bwd_9_12(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 hipError_t dispatch_bwd_13_16(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
+// the same for 16-bit features (dtype: MRP_DTYPE_BF16 or MRP_DTYPE_F16), film_mean_bwd_half_*.hip
+hipError_t dispatch_bwd_half_1_8(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
+hipError_t dispatch_bwd_half_9_12(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
+hipError_t dispatch_bwd_half_13_16(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 }  // namespace mrp_host
 

@@ -136,6 +136,8 @@ class GCN(_PackedImages, nn.Module):
         return _opt(self.opt, "gcn_return", self.__dict__.get("gcn_return_default", "aggregate"))
 
     def forward(self, g, feats: torch.Tensor = None) -> torch.Tensor:
+        """The aggregate of ``feats`` (fp32, bf16 or fp16; returned in that dtype — the encoder's logits
+        stay fp32 and the aggregation's arithmetic is fp32 either way)."""
         x = g.ndata["image"] if feats is None else feats
         if self._return_mode() == "input":
             return x  # models.py:226 returns the input; update_all's result is never read
@@ -165,7 +167,8 @@ class GCN(_PackedImages, nn.Module):
         reading x and the aggregate in place, and in backward the data-gradient kernel writing x's
         gradient half and the aggregate's gradient straight into the aggregation backward, plus the
         split-K weight-gradient kernel (``compress.FilmCompressFunction``).  With
-        ``compress.set_compress_path('library')``: the cat kernel + torch's library GEMMs."""
+        ``compress.set_compress_path('library')``: the cat kernel + torch's library GEMMs.  bf16 / fp16
+        features (a backbone under ``torch.autocast``): the 16-bit cat kernel, then ``conv(h)`` by torch."""
         x = feats
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):

@@ -222,8 +222,11 @@ int mrp_film_mean_bwd_ex(const float* grad_out, int64_t g_node_stride,
  * operation, and every stored element is rounded once, to nearest even:
  *   mrp_film_mean_fwd_t(T, x) == T(mrp_film_mean_fwd_ex(float(x)))        bit for bit,
  * likewise grad_x for graphs of <= 8 nodes; xcopy receives x's bits unchanged.  Graphs of 9..16 nodes
- * run film_bwd_dx + the film_bwd_fused Gram pass at 16 bits (no matrix-core / per-edge-slot kernel), so
- * there grad_x, like grad_gb everywhere, is summed in another order than the fp32 path's.
+ * (complete, or regular with in-degree <= 8) whose planes are whole groups of 64 pixels, with 8-byte
+ * aligned pointers and node strides that are multiples of 4, run the matrix-core backward on 16-bit
+ * features too: grad_x == T(fp32 grad_x) and grad_gb == the fp32 grad_gb, bit for bit.  Other shapes
+ * of 9..16 nodes run film_bwd_dx + the film_bwd_fused Gram pass at 16 bits (no per-edge-slot kernel);
+ * there grad_x, like grad_gb for <= 8 nodes, is summed in another order than the fp32 path's.
  * Slices are 16 bytes (8 elements; forward, <= 8 nodes), 8 bytes (4 elements) or one element, by the
  * alignment of the pointers, P and the node strides.
  */
@@ -471,7 +474,9 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * "bwd_fused_*", "bwd_regular_*"; kernel choice: "bwd_regular_mfma" (1, default: the matrix-core
  * backward for MRP_GRAPH_REGULAR graphs of 9..16 nodes), "bwd_complete_mfma" (1, default: the
  * matrix-core backward for complete graphs of 9..16 nodes too; those of <= 8 always run the VALU
- * one), "bwd_mfma_cpw" (channel blocks per wave of the matrix-core backward, 1 or 2), "bwd_pre2" (0
+ * one), "bwd_half_mfma" (1, default: 16-bit features run the matrix-core backward wherever the two
+ * knobs before choose it for fp32; 0: film_bwd_dx + the Gram pass, as for shapes the kernel does not
+ * take), "bwd_mfma_cpw" (channel blocks per wave of the matrix-core backward, 1 or 2), "bwd_pre2" (0
  * off, 1 on, 2 on unless a grad_x base is given), "fwd_regular_split" (0, default: whole planes).
  * Knobs that name a kernel accept only the kernels the library builds: "edge_split_v"
  * (mrp_edge_encoder_fwd_split: -1, default: per shape; 1 / 3: the hidden layer shared by a workgroup

@@ -13,7 +13,8 @@ REPO = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "film_mean_bwd_9_12.hip",
                                                     "film_mean_bwd_13_16.hip", "film_mean_fwd.hip",
                                                     "film_mean_bwd_half_1_8.hip", "film_mean_bwd_half_9_12.hip",
-                                                    "film_mean_bwd_half_13_16.hip", "film_mean_fwd_bf16.hip",
+                                                    "film_mean_bwd_half_13_16.hip", "film_mean_bwd_half_mfma.hip",
+                                                    "film_mean_fwd_bf16.hip",
                                                     "film_mean_fwd_f16.hip", "film_mean_bwd.hip",
                                                     "edge_encoder.hip", "frame_graph.hip",
                                                     "compress_gemm.hip", "encoder_split.hip",

@@ -1,5 +1,6 @@
 // film_mean_bwd.hip — backward C ABI (mrp_film_mean_bwd).  The kernel launches are instantiated
-// in film_mean_bwd_{1_8,9_12,13_16}.hip (split by graph size so they compile in parallel);
+// in film_mean_bwd_{1_8,9_12,13_16}.hip (split by graph size so they compile in parallel) and, for 16-bit
+// features, film_mean_bwd_half_{1_8,9_12,13_16,mfma}.hip;
 // kernels and design notes: film_mean_kernels.hpp.
 #include "film_mean_kernels.hpp"
 
@@ -129,7 +130,8 @@ int film_bwd_impl(int32_t dtype, const void* grad_out, int64_t g_node_stride, co
   Geometry g;
   const int kdeg = MRP_GRAPH_IS_REGULAR(graph_kind) ? MRP_GRAPH_REGULAR_K(graph_kind) : 0;
   if (!half && max_nodes > 8 && kdeg >= 1 && kdeg <= 8) {
-    // film_bwd_regular (fp32 features only; 16-bit ones take film_bwd_dx + the Gram pass below): 8-byte slices on 16 lanes per plane (367 us against 569 us on 64 lanes at
+    // film_bwd_regular (fp32 features only; 16-bit ones that film_bwd_mfma below does not take run
+    // film_bwd_dx + the Gram pass): 8-byte slices on 16 lanes per plane (367 us against 569 us on 64 lanes at
     // k-NN(4) N=16 C=1024 16x16): its prologue and lane reduction are amortised over more slices
     const Tuning& tu = tuning();
     vec = (vec4 && kdeg <= 4 && tu.bwd_regular_vec == 2) ? 2 : 1;
@@ -142,18 +144,22 @@ int film_bwd_impl(int32_t dtype, const void* grad_out, int64_t g_node_stride, co
   } else {
     g = make_geometry(C, P, vec, 64, 64, mrp::kMaxChanPerBlock);  // film_bwd_dx + Gram pass
   }
-  // film_bwd_mfma (fp32 features only): regular graphs of 9..16 nodes and complete graphs, whole pixel groups of 64
+  // film_bwd_mfma: regular graphs of 9..16 nodes and complete graphs, whole pixel groups of 64, 4-element
+  // slices (vec4: 16-byte aligned fp32, 8-byte aligned 16-bit features; bwd_half_mfma = 0 keeps 16-bit
+  // features on film_bwd_dx + the Gram pass)
   const bool complete = graph_kind == MRP_GRAPH_COMPLETE;
-  const bool mfma_kind = (max_nodes > 8 && kdeg >= 1 && kdeg <= 8 && tuning().bwd_regular_mfma) ||
-                         (complete && max_nodes > 8 && tuning().bwd_complete_mfma);
-  if (!half && mfma_kind && vec4 && P % 64 == 0) {
-    // per-lane row offsets are 32-bit: 15 node strides + two planes (a block's channel pair)
+  const bool mfma_kind = ((max_nodes > 8 && kdeg >= 1 && kdeg <= 8 && tuning().bwd_regular_mfma) ||
+                          (complete && max_nodes > 8 && tuning().bwd_complete_mfma)) &&
+                         (!half || tuning().bwd_half_mfma);
+  if (mfma_kind && vec4 && P % 64 == 0) {
+    // per-lane row byte offsets are 32-bit: 15 node strides + two planes (a block's channel pair)
     const int64_t lim = (int64_t)1 << 32;
-    const int64_t span = (int64_t)plane * 4 + (int64_t)P * 4;
-    bool fits = (int64_t)15 * g_node_stride * 4 + span < lim;
-    if (want_dx) fits = fits && (int64_t)15 * gx_node_stride * 4 + span < lim;
-    if (want_dx && grad_x_base) fits = fits && (int64_t)15 * base_node_stride * 4 + span < lim;
-    if (want_dgb) fits = fits && (int64_t)15 * x_node_stride * 4 + span < lim;
+    const int64_t esz = half ? 2 : 4;
+    const int64_t span = (int64_t)plane * esz + (int64_t)P * esz;
+    bool fits = (int64_t)15 * g_node_stride * esz + span < lim;
+    if (want_dx) fits = fits && (int64_t)15 * gx_node_stride * esz + span < lim;
+    if (want_dx && grad_x_base) fits = fits && (int64_t)15 * base_node_stride * esz + span < lim;
+    if (want_dgb) fits = fits && (int64_t)15 * x_node_stride * esz + span < lim;
     if (fits) {
       const int cpw = tuning().bwd_mfma_cpw >= 2 ? 2 : 1;  // instantiated: 1, 2
       g.mfma_npb = 16;

@@ -52,9 +52,10 @@ hipError_t launch_bwd_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st
   }
 }
 
-// 16-bit features (T = mrp::bf16_t / mrp::f16_t): film_bwd_fused up to 8 nodes, film_bwd_dx + the VB = 4
-// Gram pass beyond (no matrix-core or per-edge-slot kernel), slices of 4 elements (8 bytes) or 1, and no
-// PRE2 variant: half of the fp32 instantiation set per dtype (1..8 nodes: 64 kernels against 128).
+// 16-bit features (T = mrp::bf16_t / mrp::f16_t): film_bwd_fused up to 8 nodes; beyond, film_bwd_mfma<..., T>
+// where mrp_film_mean_bwd_t chose it (g.mfma_npb, launch_bwd_half_mfma) and else film_bwd_dx + the VB = 4
+// Gram pass (no per-edge-slot kernel), slices of 4 elements (8 bytes) or 1, and no PRE2 variant: half of
+// the fp32 instantiation set per dtype (1..8 nodes: 64 kernels against 128).
 template <typename T, int NT, bool COMPLETE, bool DXB>
 hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st) {
   if constexpr (NT <= 8) {
@@ -90,8 +91,17 @@ hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream
   }
 }
 
+// film_bwd_mfma<..., T> for graphs of 9..16 nodes, instantiated in film_mean_bwd_half_mfma.hip for
+// mrp::bf16_t and mrp::f16_t (12 kernels each: COMPLETE / REGULAR KMAX 4, 8 x grad_x base x blocks per wave)
+template <typename T>
+hipError_t launch_bwd_half_mfma(bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
+
 template <typename T, int NT>
 hipError_t launch_bwd_half_nt(bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
+  if (g.mfma_npb) {
+    if constexpr (NT > 8) return launch_bwd_half_mfma<T>(complete, a, g, st);
+    return hipErrorInvalidValue;  // graphs of <= 8 nodes run film_bwd_fused
+  }
   if (g.vec != 4 && g.vec != 1) return hipErrorInvalidValue;
   if (complete)
     return a.dxb ? launch_bwd_half_ntb<T, NT, true, true>(a, g, st) : launch_bwd_half_ntb<T, NT, true, false>(a, g, st);

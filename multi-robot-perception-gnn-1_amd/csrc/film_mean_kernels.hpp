@@ -1664,6 +1664,27 @@ __global__ void __launch_bounds__(kBlock) film_bwd_regular(AggArgs a) {
 // ---------------------------------------------------------------------------
 typedef float mf4 __attribute__((ext_vector_type(4)));
 
+// Four consecutive elements of T as one nontemporal access (16 bytes of fp32, 8 bytes of a 16-bit type,
+// widened exactly on load and rounded once, to nearest even, at the store).
+template <typename T>
+__device__ __forceinline__ mf4 load_mf4(const T* p) {
+  if constexpr (std::is_same<T, float>::value) {
+    return __builtin_nontemporal_load(reinterpret_cast<const mf4*>(p));
+  } else {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    return __builtin_convertvector(__builtin_nontemporal_load(reinterpret_cast<const t4*>(p)), mf4);
+  }
+}
+template <typename T>
+__device__ __forceinline__ void store_mf4(T* p, mf4 o) {
+  if constexpr (std::is_same<T, float>::value) {
+    __builtin_nontemporal_store(o, reinterpret_cast<mf4*>(p));
+  } else {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(__builtin_convertvector(o, t4), reinterpret_cast<t4*>(p));
+  }
+}
+
 // Template parameters:
 //   COMPLETE: complete graphs of exactly n = max_nodes nodes with arithmetic edge ids (the reference
 //             topology), else REGULAR(k) graphs (slot (v, j) = CSR position K v + j).
@@ -1672,7 +1693,11 @@ typedef float mf4 __attribute__((ext_vector_type(4)));
 //             16-index vn = 8 h + node, h = channel of the pair).
 //   CPW:      blocks per wave, walked in turn with the next (block, pixel group)'s loads in flight
 //             under the current group's MFMAs; workgroup = 4 waves = 4 CPW blocks, one prologue.
-template <bool COMPLETE, int NPB, int KMAX, bool DXB, int CPW>
+//   T:        the feature tensors' storage type (float, bf16_t, f16_t; strides in elements of T).  16-bit
+//             rows are 128 bytes per pixel group and every access is 8 bytes; the values are widened at
+//             the load, so registers, the LDS tile and every MFMA are the fp32 kernel's: grad_x equals
+//             the fp32 kernel's on the widened inputs rounded to T, grad_gb equals it bit for bit.
+template <bool COMPLETE, int NPB, int KMAX, bool DXB, int CPW, typename T = float>
 __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   static_assert(NPB == 16 || NPB == 8, "16-row blocks of one or two channels");
   constexpr int CB = 16 / NPB;             // channels per block
@@ -1687,6 +1712,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   // transpose tile row stride: 32 pixels + 8, so the 16-lane groups of the by-node ds_read_b128
   // (rows jl, column chunk q) cover distinct banks (+4 was 2-way)
   constexpr int TR = 32 + 8;
+  constexpr uint32_t ES = (uint32_t)sizeof(T);  // bytes per feature element
   extern __shared__ float4 smem_f4[];
   float* smem = reinterpret_cast<float*>(smem_f4);
   float* Wt = smem;                   // [CPB][CS]       Wt[u][v] (rows of WR); each channel's rows become D[v][u]
@@ -1752,14 +1778,14 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     hq[bb] = h;
     nvalid[bb] = node < n;
     const uint32_t nd = (uint32_t)min(node, n - 1);
-    const uint32_t hp = (uint32_t)h * (uint32_t)a.P * 4u + (uint32_t)jl * 16u;
-    goff4[bb] = nd * (uint32_t)a.gs * 4u + hp;
-    ooff4[bb] = nd * (uint32_t)a.os * 4u + hp;
-    boff4[bb] = DXB ? nd * (uint32_t)a.dxbs * 4u + hp : 0u;
+    const uint32_t hp = (uint32_t)h * (uint32_t)a.P * ES + (uint32_t)jl * 4u * ES;
+    goff4[bb] = nd * (uint32_t)a.gs * ES + hp;
+    ooff4[bb] = nd * (uint32_t)a.os * ES + hp;
+    boff4[bb] = DXB ? nd * (uint32_t)a.dxbs * ES + hp : 0u;
   }
   const int hx = jl / NPB, nx = jl % NPB;
   const int ngroups = a.P >> 6;
-  float* T = Tt + w * 16 * TR;
+  float* Tw = Tt + w * 16 * TR;
   // the wave's blocks: channels c0 + (w + 4 i) CB + h
   const int nblk = max(0, min(CPW, (a.C - c0 - w * CB + 4 * CB - 1) / (4 * CB)));
   const int nsteps = nblk * ngroups;
@@ -1773,31 +1799,30 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   auto load_step = [&](int st, mf4 (&gr)[4], mf4 (&xr)[4], mf4 (&br)[DXB ? 4 : 1]) {
     const int i = st / ngroups, g = st - i * ngroups;
     const int c = blk_c(i);
-    const float* gbase = static_cast<const float*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c * a.P;
+    const T* gbase = static_cast<const T*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c * a.P;
     const bool h1 = CB == 1 || hvalid(i, 1);
 #pragma unroll
     for (int bb = 0; bb < 4; ++bb) {
-      const uint32_t off = goff4[bb] - (h1 ? 0u : (uint32_t)hq[bb] * (uint32_t)a.P * 4u);
-      gr[bb] = __builtin_nontemporal_load(reinterpret_cast<const mf4*>(at_bytes(gbase, off + (uint32_t)g * 256u)));
+      const uint32_t off = goff4[bb] - (h1 ? 0u : (uint32_t)hq[bb] * (uint32_t)a.P * ES);
+      gr[bb] = load_mf4(at_bytes(gbase, off + (uint32_t)g * 64u * ES));
     }
     if constexpr (DXB) {
       if (a.want_dx) {
-        const float* dxbase = static_cast<const float*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c * a.P;
+        const T* dxbase = static_cast<const T*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c * a.P;
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) {
-          const uint32_t off = boff4[bb] - (h1 ? 0u : (uint32_t)hq[bb] * (uint32_t)a.P * 4u);
-          br[bb] = __builtin_nontemporal_load(reinterpret_cast<const mf4*>(at_bytes(dxbase, off + (uint32_t)g * 256u)));
+          const uint32_t off = boff4[bb] - (h1 ? 0u : (uint32_t)hq[bb] * (uint32_t)a.P * ES);
+          br[bb] = load_mf4(at_bytes(dxbase, off + (uint32_t)g * 64u * ES));
         }
       }
     }
     if (a.want_dgb) {
-      const float* xbase = static_cast<const float*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c * a.P;
-      const uint32_t xo = (uint32_t)min(nx, n - 1) * (uint32_t)a.xs * 4u + (uint32_t)(h1 ? hx : 0) * (uint32_t)a.P * 4u +
-                          (uint32_t)q * 16u;
+      const T* xbase = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c * a.P;
+      const uint32_t xo = (uint32_t)min(nx, n - 1) * (uint32_t)a.xs * ES + (uint32_t)(h1 ? hx : 0) * (uint32_t)a.P * ES +
+                          (uint32_t)q * 4u * ES;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        xr[t] = __builtin_nontemporal_load(
-            reinterpret_cast<const mf4*>(at_bytes(xbase, xo + (uint32_t)g * 256u + (uint32_t)t * 64u)));
+        xr[t] = load_mf4(at_bytes(xbase, xo + (uint32_t)g * 64u * ES + (uint32_t)t * 16u * ES));
     }
   };
 
@@ -1866,7 +1891,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     for (int bb = 0; bb < 4; ++bb)
       if (!rvalid[bb]) gr[bb] = mf4{0.f, 0.f, 0.f, 0.f};
     if (a.want_dx) {
-      float* obase = static_cast<float*>(a.out) + (int64_t)node0 * a.os + (int64_t)c * a.P;
+      T* obase = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c * a.P;
       mf4 acc[4];
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc) {
@@ -1880,7 +1905,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
         if (a.self_scale != 0.f) o += a.self_scale * gr[r];  // residual epilogue
         if (rvalid[r]) {
           if constexpr (DXB) o += br[r];
-          __builtin_nontemporal_store(o, reinterpret_cast<mf4*>(at_bytes(obase, ooff4[r] + (uint32_t)g * 256u)));
+          store_mf4(at_bytes(obase, ooff4[r] + (uint32_t)g * 64u * ES), o);
         }
       }
     }
@@ -1890,7 +1915,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
       for (int hh = 0; hh < 2; ++hh) {
         if ((jl >> 3) == hh) {  // lanes with jl in [8hh, 8hh + 8) hold pixels [32hh, 32hh + 32) of the group
 #pragma unroll
-          for (int bb = 0; bb < 4; ++bb) *reinterpret_cast<mf4*>(T + (4 * q + bb) * TR + 4 * (jl & 7)) = gr[bb];
+          for (int bb = 0; bb < 4; ++bb) *reinterpret_cast<mf4*>(Tw + (4 * q + bb) * TR + 4 * (jl & 7)) = gr[bb];
         }
         // the tile is exchanged between lanes of this wave only: LDS executes a wave's accesses in
         // order, so a compiler-level barrier (no reordering across it) is all the ordering needed
@@ -1898,7 +1923,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-          const mf4 gn = *reinterpret_cast<const mf4*>(T + jl * TR + 16 * t2 + 4 * q);
+          const mf4 gn = *reinterpret_cast<const mf4*>(Tw + jl * TR + 16 * t2 + 4 * q);
           const mf4 xv = xr[2 * hh + t2];
 #pragma unroll
           for (int cc = 0; cc < 4; ++cc) dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(gn[cc], xv[cc], dacc, 0, 0, 0);

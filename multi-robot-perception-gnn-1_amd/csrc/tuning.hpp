@@ -31,6 +31,10 @@ struct Tuning {
   int bwd_regular_mfma = 1;
   int bwd_complete_mfma = 1;
   int bwd_mfma_cpw = 2;  // film_bwd_mfma: 16-row blocks per wave (1 or 2)
+  // 16-bit features on graphs of 9..16 nodes: 1 = film_bwd_mfma<..., T> (8-byte accesses on the fp32
+  // kernel's 64-pixel groups) wherever the two knobs above choose the kernel for fp32, 0 = film_bwd_dx +
+  // the Gram pass (tools/bench_half_io.py --knob bwd_half_mfma=0,1)
+  int bwd_half_mfma = 1;
 
   // split-bf16 compress forward / data gradient (compress_split.hip): -1 per shape, 7 (256-row
   // workgroups on 16x16x32 MFMAs, where M % 256 == 0) or 2 (128-row workgroups on 32x32x16)

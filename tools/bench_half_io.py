@@ -9,9 +9,16 @@ Protocol: hipEvents around every call, the host running ahead of
 holds device time only (a few milliseconds of copies are queued first); 5 warm-ups; the median of ``--iters`` (>= 50) timed calls; input/output sets
 rotated over a total footprint above 512 MB so no call finds its operands in the 256 MB last-level cache.
 
-Prints one JSON line and writes ``profiles/half_io_bench.json``.
+``--knob NAME=V0,V1[,...]`` (e.g. ``bwd_half_mfma=0,1``) adds an A/B of the 16-bit backward on the rows
+of 9..16-node graphs: one timed loop in which the knob values and the fp32 backward take turns call by call
+(settings interleaved, so drift of the box hits every variant alike), the median per variant
+(``bwd_ab_us``), each variant's fraction of the copy ceiling and ``t / t_fp32``.
 
-    python tools/bench_half_io.py [--iters 50] [--shapes headline,small_planes,knn] [--out PATH]
+Prints one JSON line and writes ``profiles/half_io_bench.json`` (with ``--knob``:
+``profiles/half_io_bench_mfma.json``).
+
+    python tools/bench_half_io.py [--iters 50] [--shapes headline,small_planes,knn] [--knob bwd_half_mfma=0,1]
+                                  [--out PATH]
 """
 import argparse
 import ctypes
@@ -35,6 +42,8 @@ SHAPES = {
     "headline": (32, 8, None, 512, 32, 32),
     "small_planes": (32, 8, None, 1280, 8, 8),
     "knn": (8, 16, 4, 1024, 16, 16),
+    "complete16": (8, 16, None, 1024, 16, 16),
+    "complete12_small_planes": (32, 12, None, 1280, 8, 8),  # one 64-pixel group per plane
 }
 DTYPES = [("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp16", torch.float16)]
 WARMUP = 5
@@ -67,7 +76,35 @@ def timed(calls, iters, blocker):
     return statistics.median(a.elapsed_time(b) for a, b in ev) * 1e3
 
 
-def bench_shape(name, dev, iters):
+def timed_interleaved(variants, iters, blocker):
+    """Medians (us) of several variants timed in one loop, taking turns call by call.  variants: name ->
+    (setup or None, calls); setup() runs on the host before each of the variant's calls (a tuning knob: it
+    decides the launch, so it holds for the call enqueued right after it)."""
+    turn = 0  # counts every call: variants that share operand sets never follow each other on one set
+    for name, (setup, calls) in variants.items():
+        for i in range(WARMUP):
+            if setup:
+                setup()
+            calls[turn % len(calls)]()
+            turn += 1
+    torch.cuda.synchronize()
+    ev = {name: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+          for name in variants}
+    blocker()
+    for i in range(iters):
+        for name, (setup, calls) in variants.items():
+            if setup:
+                setup()
+            a, b = ev[name][i]
+            a.record()
+            calls[turn % len(calls)]()
+            b.record()
+            turn += 1
+    torch.cuda.synchronize()
+    return {name: statistics.median(a.elapsed_time(b) for a, b in ev[name]) * 1e3 for name in variants}
+
+
+def bench_shape(name, dev, iters, knob=None):
     B, n, knn, C, H, W = SHAPES[name]
     g = frames(B, n, knn)
     csr = g.csr(dev)
@@ -88,29 +125,38 @@ def bench_shape(name, dev, iters):
         for _ in range(40):
             _lib.check(lib.mrp_stream_copy(ptr(block_a), ptr(block_b), block_a.numel(), stream), "mrp_stream_copy")
 
-    rows = {}
-    for label, T in DTYPES:
-        elem = torch.empty((), dtype=T).element_size()
-        tensor_bytes = Nt * C * P * elem
-        # sets of (x, out, grad_out, grad_x, grad_gb): rotate enough of them to exceed the footprint
-        nsets = max(2, -(-MIN_FOOTPRINT // (2 * tensor_bytes)) + 1)
+    def make_sets(T):
+        """Sets of (x, out, grad_out, grad_x, grad_gb): enough of them, rotated, to exceed the footprint."""
+        tensor_bytes = Nt * C * P * torch.empty((), dtype=T).element_size()
         sets = []
-        for _ in range(nsets):
+        for _ in range(max(2, -(-MIN_FOOTPRINT // (2 * tensor_bytes)) + 1)):
             x = torch.randn(Nt, C, H, W, device=dev, generator=gen).to(T)
             G = torch.randn(Nt, C, H, W, device=dev, generator=gen).to(T)
             sets.append((x, torch.empty_like(x), G, torch.empty_like(x),
                          torch.empty(E, C, 2, device=dev, dtype=torch.float32)))
+        return sets
+
+    def bwd_calls(T, sets):
+        dt = aggregate.FEATURE_DTYPES[T]
+
+        def bwd(s):
+            x, _, G, dx, dgb = s
+            args = (dt, ptr(G), stride, ptr(x), stride) + graph + (ptr(dx), stride, None, 0, ptr(dgb), None, stream)
+            return lambda: _lib.check(lib.mrp_film_mean_bwd_t(*args), "mrp_film_mean_bwd_t")
+        return [bwd(s) for s in sets]
+
+    rows = {}
+    for label, T in DTYPES:
+        elem = torch.empty((), dtype=T).element_size()
+        tensor_bytes = Nt * C * P * elem
+        sets = make_sets(T)
+        nsets = len(sets)
 
         dt = aggregate.FEATURE_DTYPES[T]  # fp32: the typed entry points forward to the fp32 implementation
 
         def fwd(s):
             args = (dt, ptr(s[0]), stride) + graph + (ptr(s[1]), stride, None, stream)
             return lambda: _lib.check(lib.mrp_film_mean_fwd_t(*args), "mrp_film_mean_fwd_t")
-
-        def bwd(s):
-            x, _, G, dx, dgb = s
-            args = (dt, ptr(G), stride, ptr(x), stride) + graph + (ptr(dx), stride, None, 0, ptr(dgb), None, stream)
-            return lambda: _lib.check(lib.mrp_film_mean_bwd_t(*args), "mrp_film_mean_bwd_t")
 
         def copy(nbytes):
             half = (nbytes // 2 + 15) // 16 * 16  # read `half`, write `half`
@@ -123,9 +169,23 @@ def bench_shape(name, dev, iters):
 
         fwd_bytes, bwd_bytes = 2 * tensor_bytes, 3 * tensor_bytes
         t_fwd = timed([fwd(s) for s in sets], iters, blocker)
-        t_bwd = timed([bwd(s) for s in sets], iters, blocker)
+        t_bwd = timed(bwd_calls(T, sets), iters, blocker)
         t_cf = timed(copy(fwd_bytes), iters, blocker)
         t_cb = timed(copy(bwd_bytes), iters, blocker)
+        ab = None
+        if knob is not None and T != torch.float32 and n > 8:
+            kname, values = knob
+
+            def setter(v):
+                return lambda: _lib.check(lib.mrp_tuning_set(kname.encode(), v), "mrp_tuning_set")
+            sets32 = make_sets(torch.float32)
+            variants = {f"{kname}={v}": (setter(v), bwd_calls(T, sets)) for v in values}
+            variants["fp32"] = (None, bwd_calls(torch.float32, sets32))
+            try:
+                ab = timed_interleaved(variants, iters, blocker)
+            finally:
+                _lib.check(lib.mrp_tuning_set(b"reset", 0), "mrp_tuning_set")
+            del sets32
         del sets
         torch.cuda.empty_cache()
         rows[label] = {
@@ -136,6 +196,10 @@ def bench_shape(name, dev, iters):
             "fwd_ceiling_frac": round(t_cf / t_fwd, 3), "bwd_ceiling_frac": round(t_cb / t_bwd, 3),
             "rotated_sets": nsets,
         }
+        if ab is not None:
+            rows[label]["bwd_ab_us"] = {k: round(v, 2) for k, v in ab.items()}
+            rows[label]["bwd_ab_vs_fp32"] = {k: round(v / ab["fp32"], 3) for k, v in ab.items() if k != "fp32"}
+            rows[label]["bwd_ab_ceiling_frac"] = {k: round(t_cb / v, 3) for k, v in ab.items() if k != "fp32"}
     for label in ("bf16", "fp16"):
         rows[label]["fwd_vs_fp32"] = round(rows[label]["fwd_us"] / rows["fp32"]["fwd_us"], 3)
         rows[label]["bwd_vs_fp32"] = round(rows[label]["bwd_us"] / rows["fp32"]["bwd_us"], 3)
@@ -146,15 +210,24 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "half_io_bench.json"))
+    ap.add_argument("--knob", default=None, help="NAME=V0,V1[,...]: A/B of the 16-bit backward over a tuning knob")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.iters < 50:
         ap.error("--iters must be >= 50 (median of at least 50 timed calls)")
+    knob = None
+    if a.knob is not None:
+        kname, _, vals = a.knob.partition("=")
+        if not kname or not vals:
+            ap.error("--knob takes NAME=V0,V1[,...]")
+        knob = (kname, [int(v) for v in vals.split(",")])
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "half_io_bench_mfma.json" if knob else "half_io_bench.json")
     dev = torch.device("cuda:0")
     result = {"tool": "bench_half_io", "device": torch.cuda.get_device_name(dev), "iters": a.iters,
-              "warmup": WARMUP, "abi": _lib.ABI_VERSION, "shapes": {}}
+              "warmup": WARMUP, "abi": _lib.ABI_VERSION, "knob": a.knob, "shapes": {}}
     for name in a.shapes.split(","):
-        result["shapes"][name] = bench_shape(name, dev, a.iters)
+        result["shapes"][name] = bench_shape(name, dev, a.iters, knob)
     line = json.dumps(result)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:

@@ -125,6 +125,7 @@ _ENC_STREAM = os.environ.get("MRP_ENCODER_STREAM", "1") != "0"
 # bookkeeping (its waits and the join, ~10 us of host time) would cost more than the overlap saves
 _ENC_STREAM_MIN_WORK = 1 << 18
 _enc_streams = {}
+# both describe the device's current encoder stream and are dropped with it (set_encoder_stream_priority)
 _waited = {}       # device index -> ids of readiness events the encoder stream already waits behind
 _recorded = {}     # device index -> {id(tensor): weakref} already recorded on the encoder stream
 _ready = {}        # id(tensor) -> (weakref, version, event)
@@ -134,6 +135,15 @@ _image_ready = {}  # id(packed image) -> (weakref, event recorded after its pack
 def set_encoder_stream(on: bool) -> None:
     global _ENC_STREAM
     _ENC_STREAM = bool(on)
+
+
+def set_encoder_stream_min_work(n: int) -> int:
+    """Set the E x C threshold below which the encoder stays on the caller's stream (default 1 << 18);
+    returns the previous value.  Tests set 0 to run a tiny encoder on the encoder stream."""
+    global _ENC_STREAM_MIN_WORK
+    prev = _ENC_STREAM_MIN_WORK
+    _ENC_STREAM_MIN_WORK = int(n)
+    return prev
 
 
 def _record(dev: torch.device) -> torch.cuda.Event:
@@ -176,6 +186,10 @@ def set_encoder_stream_priority(priority: int) -> None:
     global _ENC_PRIORITY
     _ENC_PRIORITY = int(priority)
     _enc_streams.clear()
+    # the bookkeeping below describes the streams just dropped: a new stream has passed none of their
+    # waits, and no input has been recorded on it
+    _waited.clear()
+    _recorded.clear()
 
 
 def _enc_stream(dev: torch.device) -> torch.cuda.Stream:
@@ -237,7 +251,9 @@ def _enc_begin(dev: torch.device, work: int, reads, img):
     tensor, tensor the kernel reads) pairs) and of the packed image; or None for the caller's stream
     (small encoders, stream capture, set_encoder_stream(False))."""
     if not _ENC_STREAM or work < _ENC_STREAM_MIN_WORK or torch.cuda.is_current_stream_capturing():
+        PATH_COUNTS["enc_inline"] += 1
         return None
+    PATH_COUNTS["enc_stream"] += 1
     side = _enc_stream(dev)
     waited = _waited.setdefault(dev.index, {})
 
@@ -387,7 +403,9 @@ class EdgeEncoderFunction(torch.autograd.Function):
 #: calls per encoder path ("split": mrp_edge_encoder_fwd_split,
 #: "split_train": EdgeEncoderSplitFunction, "split_padded": EdgeEncoderPaddedFunction,
 #: "autograd": EdgeEncoderFunction) — lets tests assert which
-#: kernels a forward actually ran
+#: kernels a forward actually ran; and, per "split" call, the stream it ran on ("enc_stream": the
+#: encoder stream behind its inputs' readiness events, "enc_inline": the caller's stream — a small
+#: encoder, stream capture or set_encoder_stream(False))
 PATH_COUNTS = collections.Counter()
 
 

@@ -164,16 +164,21 @@ def _forward(gcn, g, x, own_stream):
 
 
 def test_encoder_stream_ordered_after_input_writes(cuda_device):
-    """The inference encoder runs on its own stream (``encoder.set_encoder_stream``, the default), ordered
-    after the producers of what it reads, not after everything queued before it.  Its results are the
-    caller's-stream results bit for bit; in-place writes to the poses and to the weights (an optimizer
-    step), queued behind long kernels on the caller's stream, are seen by the next forward; and under
-    stream capture the layer records on one stream and replays to the same bits."""
+    """The small-encoder route of the inference encoder: at E C = 336 x 64 = 21 504, below the encoder
+    stream's threshold (``encoder._ENC_STREAM_MIN_WORK`` = 2^18), ``set_encoder_stream(True)`` (the
+    default) keeps the encoder on the caller's stream - asserted through ``PATH_COUNTS["enc_inline"]`` -
+    so this checks that the switch changes no bit there, that in-place writes to the poses, the weights
+    (an optimizer step), b2 and the features queued behind long kernels are seen by the next forward
+    (the version-keyed weight images are rebuilt), and that under stream capture the layer records on
+    one stream and replays to the same bits.  The encoder stream itself - its readiness events and the
+    join - is tested in ``test_gpu_encoder_stream.py``."""
     C = 64
     g = _headline_graph(cuda_device, B=6, C=C, H=16)
     torch.manual_seed(2)
     gcn = m.GCN(types.SimpleNamespace(feature_dim=C)).to(cuda_device)
     x = g.ndata["image"]
+    assert g.num_edges() * C < m.encoder._ENC_STREAM_MIN_WORK
+    on0, inline0 = m.encoder.PATH_COUNTS["enc_stream"], m.encoder.PATH_COUNTS["enc_inline"]
     a, b = _forward(gcn, g, x, True), _forward(gcn, g, x, False)
     assert torch.equal(a, b)
     busy = torch.randn(64 << 20, device=cuda_device)  # 256 MB: keeps the caller's stream busy
@@ -219,6 +224,9 @@ def test_encoder_stream_ordered_after_input_writes(cuda_device):
         finally:
             m.encoder.set_encoder_stream(True)
     assert all(torch.equal(a_, b_) for a_, b_ in zip(runs, refs))
+    # all 18 encoder calls so far, the 9 with the encoder stream switched on included, ran inline
+    assert m.encoder.PATH_COUNTS["enc_stream"] == on0
+    assert m.encoder.PATH_COUNTS["enc_inline"] == inline0 + 18
     e = f
     # stream capture: one stream, replayed
     side = torch.cuda.Stream()

@@ -334,6 +334,48 @@ int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_stride, const
                                   float* gw, float* gbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * The compress forward and both gradients on bf16 / fp16 feature maps (compress_half.hip; dtype is
+ * MRP_DTYPE_BF16 or MRP_DTYPE_F16 = T, the storage type of x, agg, y, gy, gx and gagg; the parameters
+ * and their gradients are fp32).  The same products as the _split entry points, one
+ * v_mfma_f32_16x16x32_{bf16,f16} per product:
+ *   mrp_compress_pack_t_bytes(M, K)   bytes of a packed M x K operand, 2 per element (0 unless
+ *                                     M % 32 == 0 and K % 32 == 0)
+ *   mrp_compress_pack_t               A = w (or w^T, as mrp_compress_split_pack) rounded once to T, round
+ *                                     to nearest even -> packed (16-byte aligned)
+ *   mrp_compress_fwd_t                y = T(W_T [x; agg] + bias): fp32 accumulation, the fp32 bias (C, may
+ *                                     be NULL) added to the fp32 sum, one rounding at the store;
+ *                                     packed = pack_t(w, 2C, 0, C, 2C)
+ *   mrp_compress_bwd_data_t           [gx; gagg] = T(W_T^T gy), packed = pack_t(w, 2C, 1, 2C, C); gx and
+ *                                     gagg are separate node-major outputs with their own node strides
+ *   mrp_compress_bwd_weight_t         gw (C, 2C) = sum_n gy[n] [x[n]; agg[n]]^T and gbias (C, may be NULL)
+ *                                     = sum gy, accumulated and stored in fp32 (never rounded to T);
+ *                                     K = num_nodes P split over workgroups into fp32 partial tiles in
+ *                                     workspace (mrp_compress_bwd_weight_t_workspace bytes, 16-byte
+ *                                     aligned; 0: none needed), summed in a fixed order: deterministic
+ * Before any launch: MRP_DTYPE_F32 or an unknown dtype, a NULL pointer with work to do, a node stride
+ * below C P, a pointer that is not 16-byte aligned, a node stride that is not a multiple of 8 elements
+ * or a workspace that is too small return hipErrorInvalidValue; zero sizes return success without a
+ * launch (an empty weight-gradient sum zeroes gw / gbias).  Shapes the kernels do not tile return
+ * hipErrorNotSupported: C % 32 != 0, P % 8 != 0 (forward, data gradient), P % 32 != 0 (weight
+ * gradient), an operand or output node range beyond 31-bit byte offsets — and every shape while the
+ * tuning knob "compress_half" is 0.  No host synchronisation; stream-capturable.
+ */
+int64_t mrp_compress_pack_t_bytes(int32_t M, int32_t K);
+int mrp_compress_pack_t(int32_t dtype, const float* w, int64_t ld, int32_t transpose, int32_t M, int32_t K,
+                        void* packed, void* stream);
+int mrp_compress_fwd_t(int32_t dtype, const void* x, int64_t x_node_stride, const void* agg, int64_t agg_node_stride,
+                       int32_t num_nodes, int32_t C, int32_t P, const void* packed_w, const float* bias, void* y,
+                       int64_t y_node_stride, void* stream);
+int mrp_compress_bwd_data_t(int32_t dtype, const void* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C,
+                            int32_t P, const void* packed_wt, void* gx, int64_t gx_node_stride, void* gagg,
+                            int64_t gagg_node_stride, void* stream);
+int64_t mrp_compress_bwd_weight_t_workspace(int32_t num_nodes, int32_t C, int32_t P);
+int mrp_compress_bwd_weight_t(int32_t dtype, const void* gy, int64_t gy_node_stride, const void* x,
+                              int64_t x_node_stride, const void* agg, int64_t agg_node_stride, int32_t num_nodes,
+                              int32_t C, int32_t P, float* gw, float* gbias, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
+/*
  * First layer of the edge encoder, dgl/model/models.py:147-148:  h = relu(pose W1^T + b1).
  *   pose (num_edges, 9), w1 (C, 9) (nn.Linear weight layout), b1 (C) -> h (num_edges, C), fp32.
  * The second Linear is mrp_edge_logits_fwd and its Sigmoid is fused into the aggregation
@@ -491,12 +533,16 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * forward / data gradient, "nt_group" (the same, default 0) for the weight gradient; "enc_bwd_psa"
  * (mrp_edge_encoder_bwd_fused given w2T_packed: 2 default = both products read their A operand
  * pre-split, dz^T written as a packed image; 1 = only W2^T's image; 0 = both split in the kernel);
- * "enc_s1" / "enc_s2" (its two products' split-K counts, 0 = the planner's). */
+ * "enc_s1" / "enc_s2" (its two products' split-K counts, 0 = the planner's); "compress_half" (1
+ * default; 0 = the bf16 / fp16 compress entry points decline every shape, for A/B runs);
+ * "half_nt_splits" (mrp_compress_bwd_weight_t's split-K count, 0 default = the planner's, 1..256). */
 int mrp_tuning_set(const char* name, int32_t value);
 
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
  * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature
- * tensors, enum mrp_dtype); 21: v19 plus
+ * tensors, enum mrp_dtype) and, added since without a new number (nothing existing changed), the
+ * typed compress entry points mrp_compress_pack_t_bytes / _pack_t / _fwd_t / _bwd_data_t /
+ * _bwd_weight_t_workspace / _bwd_weight_t and the knobs "compress_half" / "half_nt_splits"; 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

@@ -38,6 +38,12 @@ EXPORTED_SYMBOLS = (
     "mrp_compress_bwd_data_split",
     "mrp_compress_bwd_weight_split_workspace",
     "mrp_compress_bwd_weight_split",
+    "mrp_compress_pack_t_bytes",
+    "mrp_compress_pack_t",
+    "mrp_compress_fwd_t",
+    "mrp_compress_bwd_data_t",
+    "mrp_compress_bwd_weight_t_workspace",
+    "mrp_compress_bwd_weight_t",
     "mrp_edge_hidden_fwd",
     "mrp_edge_logits_fwd",
     "mrp_edge_encoder_pack_bytes",
@@ -146,6 +152,18 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_compress_bwd_weight_split_workspace.restype = ctypes.c_int64
     lib.mrp_compress_bwd_weight_split.argtypes = lib.mrp_compress_bwd_weight.argtypes
     lib.mrp_compress_bwd_weight_split.restype = ctypes.c_int
+    lib.mrp_compress_pack_t_bytes.argtypes = [_I32, _I32]
+    lib.mrp_compress_pack_t_bytes.restype = ctypes.c_int64
+    lib.mrp_compress_pack_t.argtypes = [_I32] + lib.mrp_compress_split_pack.argtypes
+    lib.mrp_compress_pack_t.restype = ctypes.c_int
+    lib.mrp_compress_fwd_t.argtypes = [_I32] + lib.mrp_compress_fwd_split.argtypes
+    lib.mrp_compress_fwd_t.restype = ctypes.c_int
+    lib.mrp_compress_bwd_data_t.argtypes = [_I32] + lib.mrp_compress_bwd_data_split.argtypes
+    lib.mrp_compress_bwd_data_t.restype = ctypes.c_int
+    lib.mrp_compress_bwd_weight_t_workspace.argtypes = [_I32, _I32, _I32]
+    lib.mrp_compress_bwd_weight_t_workspace.restype = ctypes.c_int64
+    lib.mrp_compress_bwd_weight_t.argtypes = [_I32] + lib.mrp_compress_bwd_weight.argtypes
+    lib.mrp_compress_bwd_weight_t.restype = ctypes.c_int
     lib.mrp_edge_hidden_fwd.argtypes = [_P, _P, _P, _I32, _I32, _P, _P]
     lib.mrp_edge_hidden_fwd.restype = ctypes.c_int
     lib.mrp_edge_logits_fwd.argtypes = [_P, _I32, _I32, _P, _P, _P, _P]

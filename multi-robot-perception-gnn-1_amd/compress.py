@@ -27,9 +27,19 @@ H W % 32 != 0 — none of them a reference configuration: the reference's planes
 ``image_size/32`` squares, 8 x 8 at its default) run the same kernels on zero-padded operands
 (:func:`_fwd`, :func:`_bwd_data`, :func:`_bwd_weight`); ``set_compress_path("library")`` runs
 torch's own GEMMs everywhere, for A/B measurements only.
+
+bf16 / fp16 feature maps (a backbone under ``torch.autocast``; the parameters stay fp32) run the same
+three products natively (``csrc/compress_half.hip``: ``mrp_compress_fwd_t`` / ``_bwd_data_t`` /
+``_bwd_weight_t``): the weight is rounded once to the feature type T when it is packed, every product
+of two T values is exact in the fp32 accumulator, the fp32 bias is added to the fp32 sum, outputs and
+data gradients are rounded once at the store, and ``dW`` / ``db`` are accumulated and stored in fp32.
+Their tiles need C % 32 == 0 and H W % 8 == 0 (32 for the weight gradient); other shapes are
+zero-padded as above.  :func:`set_half_compress` ``("torch")`` restores the earlier route (the 16-bit
+cat kernel + torch's convolution) for A/B runs; :data:`PATH_COUNTS` counts the launches per route.
 """
 from __future__ import annotations
 
+import collections
 import weakref
 
 import torch
@@ -40,6 +50,32 @@ _PATH = ["split"]
 # products the "split" path runs on the split-bf16 kernels (the rest on the fp32 MFMA): "fwd", "dgrad",
 # "wgrad" (set_compress_path(..., split_ops=...); for A/B and accuracy studies)
 _SPLIT_OPS = {"fwd", "dgrad", "wgrad"}
+
+
+#: 16-bit feature dtypes of the native compress -> enum mrp_dtype, and the counter keys of every dtype
+HALF_DTYPES = {torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+_KEYS = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+
+#: Which route ran: ``fwd_*`` / ``dgrad_*`` / ``wgrad_*`` for each of ``f32`` / ``bf16`` / ``f16`` count
+#: the kernel launches of this module per feature dtype; ``torch_16`` counts 16-bit layers handed to
+#: torch's convolution (:func:`compress_1x1` with ``set_half_compress("torch")``, or a conv stored in T).
+PATH_COUNTS = collections.Counter()
+
+_HALF = ["native"]
+
+
+def set_half_compress(route: str) -> str:
+    """Route of a bf16 / fp16 ``cat_compress`` layer with fp32 parameters: ``"native"`` (default) the
+    kernels of ``compress_half.hip``; ``"torch"`` the 16-bit cat kernel followed by ``conv(h)``, torch's
+    own convolution (needs ``torch.autocast``), for A/B runs.  Returns the previous value."""
+    if route not in ("native", "torch"):
+        raise ValueError("half compress route must be 'native' or 'torch'")
+    prev, _HALF[0] = _HALF[0], route
+    return prev
+
+
+def half_compress() -> str:
+    return _HALF[0]
 
 
 def _split(op: str) -> bool:
@@ -77,23 +113,33 @@ def clear_packed_weights() -> None:
     _padded_w.clear()
 
 
-def packed_weight(weight: torch.Tensor, kind: str) -> torch.Tensor:
+def packed_weight(weight: torch.Tensor, kind: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """``mrp_compress_split_pack`` image of the (C, 2C[, 1, 1]) weight: ``"fwd"`` packs W (M = C,
-    K = 2C) for the forward, ``"bwd"`` packs W^T (M = 2C, K = C) for the data gradient."""
+    K = 2C) for the forward, ``"bwd"`` packs W^T (M = 2C, K = C) for the data gradient.  ``dtype``
+    bf16 / fp16: the ``mrp_compress_pack_t`` image, the weight rounded once to that type (cached per
+    weight version, kind and dtype)."""
     from .aggregate import _ptr, _stream
     key = (weight.data_ptr(), weight._version, weight.device.index)
     entry = _packed.get(id(weight))
     slot = entry[1] if entry is not None and entry[0]() is weight else None
+    kind, op = (kind if dtype == torch.float32 else (kind, dtype)), kind
     if slot is not None and kind in slot and slot[kind][0] == key:
         return slot[kind][1]
     C = weight.shape[0]
     w = _weight2d(weight)
-    M, K, trans = (C, 2 * C, 0) if kind == "fwd" else (2 * C, C, 1)
+    M, K, trans = (C, 2 * C, 0) if op == "fwd" else (2 * C, C, 1)
     lib = _lib.load_library()
-    img = torch.empty((int(lib.mrp_compress_split_pack_bytes(M, K)) + 3) // 4, device=w.device, dtype=torch.float32)
-    with torch.cuda.device(w.device):
-        _lib.check(lib.mrp_compress_split_pack(_ptr(w), 2 * C, trans, M, K, _ptr(img), _stream(w.device)),
-                   "mrp_compress_split_pack")
+    if dtype == torch.float32:
+        img = torch.empty((int(lib.mrp_compress_split_pack_bytes(M, K)) + 3) // 4, device=w.device,
+                          dtype=torch.float32)
+        with torch.cuda.device(w.device):
+            _lib.check(lib.mrp_compress_split_pack(_ptr(w), 2 * C, trans, M, K, _ptr(img), _stream(w.device)),
+                       "mrp_compress_split_pack")
+    else:
+        img = torch.empty((int(lib.mrp_compress_pack_t_bytes(M, K)) + 3) // 4, device=w.device, dtype=torch.float32)
+        with torch.cuda.device(w.device):
+            _lib.check(lib.mrp_compress_pack_t(HALF_DTYPES[dtype], _ptr(w), 2 * C, trans, M, K, _ptr(img),
+                                               _stream(w.device)), "mrp_compress_pack_t")
     if slot is None:
         slot = {}
         wid = id(weight)
@@ -107,11 +153,11 @@ def compress_path() -> str:
 
 
 def _nstride(t: torch.Tensor):
-    """Node stride of an (N, C, H, W) fp32 tensor laid out as the kernels need (each node's C H W
-    block contiguous, 16-byte aligned, stride % 4 == 0), else None."""
+    """Node stride of an (N, C, H, W) fp32 / bf16 / fp16 tensor laid out as the kernels need (each
+    node's C H W block contiguous, 16-byte aligned, stride a multiple of 16 bytes), else None."""
     from .aggregate import node_stride
     s = node_stride(t)
-    if s is None or s % 4 != 0 or t.data_ptr() % 16 != 0:
+    if s is None or s % (16 // t.element_size()) != 0 or t.data_ptr() % 16 != 0:
         return None
     return s
 
@@ -138,9 +184,14 @@ def conv_is_plain_1x1(conv: torch.nn.Conv2d, C: int) -> bool:
             and conv.weight.dtype == torch.float32)
 
 
-def kernels_supported(C: int, P: int) -> bool:
-    """The forward and data-gradient kernels: C % 32 == 0, P % 4 == 0 (``include/mrp_gnn.h``)."""
-    return C > 0 and P > 0 and C % 32 == 0 and P % 4 == 0
+def _pixel_multiple(dtype: torch.dtype) -> int:
+    return 8 if dtype in HALF_DTYPES else 4  # 16-byte row pieces
+
+
+def kernels_supported(C: int, P: int, dtype: torch.dtype = torch.float32) -> bool:
+    """The forward and data-gradient kernels: C % 32 == 0, P % 4 == 0 — P % 8 == 0 for bf16 / fp16
+    features (``include/mrp_gnn.h``)."""
+    return C > 0 and P > 0 and C % 32 == 0 and P % _pixel_multiple(dtype) == 0
 
 
 def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
@@ -148,16 +199,24 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
     (``mrp_compress_fwd``); x and a are (N, C, H, W), e.g. views of a cat buffer's halves."""
     from .aggregate import _ptr, _stream
     n, C, H, W = x.shape
+    dtype = x.dtype  # the feature dtype: a is cast to it, y is allocated in it
+    if a.dtype != dtype:
+        a = a.to(dtype)
     x, xs = _node_major(x)
     a, as_ = _node_major(a)
     w = _weight2d(weight)
     b = bias.detach() if bias is not None else None
     if b is not None and (b.dtype != torch.float32 or not b.is_contiguous()):
         b = b.float().contiguous()
-    y = torch.empty((n, C, H, W), device=x.device, dtype=torch.float32)
+    y = torch.empty((n, C, H, W), device=x.device, dtype=dtype)
     lib = _lib.load_library()
+    PATH_COUNTS["fwd_" + _KEYS[dtype]] += 1
     with torch.cuda.device(x.device):
-        if _split("fwd"):
+        if dtype in HALF_DTYPES:
+            img = packed_weight(weight, "fwd", dtype)
+            _lib.check(lib.mrp_compress_fwd_t(HALF_DTYPES[dtype], _ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img),
+                                              _ptr(b), _ptr(y), C * H * W, _stream(x.device)), "mrp_compress_fwd_t")
+        elif _split("fwd"):
             img = packed_weight(weight, "fwd")
             _lib.check(lib.mrp_compress_fwd_split(_ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img), _ptr(b), _ptr(y),
                                                   C * H * W, _stream(x.device)), "mrp_compress_fwd_split")
@@ -167,20 +226,31 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
     return y
 
 
-def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor = None, ga: torch.Tensor = None):
+def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor = None, ga: torch.Tensor = None,
+                           dtype: torch.dtype = None):
     """(gx, ga) = (W[:, :C]^T gy, W[:, C:]^T gy) per node (``mrp_compress_bwd_data``), written into
-    the given (N, C, H, W) outputs (e.g. the halves of a cat buffer's gradient) or new tensors."""
+    the given (N, C, H, W) outputs (e.g. the halves of a cat buffer's gradient) or new tensors.  The
+    feature dtype is the given outputs', else ``dtype``, else gy's; gy is cast to it."""
     from .aggregate import _ptr, _stream
     n, C, H, W = gy.shape
     lib = _lib.load_library()
+    dtype = gx.dtype if gx is not None else ga.dtype if ga is not None else dtype if dtype is not None else gy.dtype
+    if gy.dtype != dtype:
+        gy = gy.to(dtype)
     gy, gs = _node_major(gy)
-    gx = torch.empty((n, C, H, W), device=gy.device, dtype=torch.float32) if gx is None else gx
-    ga = torch.empty((n, C, H, W), device=gy.device, dtype=torch.float32) if ga is None else ga
+    gx = torch.empty((n, C, H, W), device=gy.device, dtype=dtype) if gx is None else gx
+    ga = torch.empty((n, C, H, W), device=gy.device, dtype=dtype) if ga is None else ga
     gxs, gas = _nstride(gx), _nstride(ga)
-    if gxs is None or gas is None:
-        raise ValueError("compress_backward_data: outputs must be node-major fp32, 16-byte aligned")
+    if gxs is None or gas is None or gx.dtype != dtype or ga.dtype != dtype:
+        raise ValueError("compress_backward_data: outputs must be node-major in one feature dtype, 16-byte aligned")
     st = _stream(gy.device)
+    PATH_COUNTS["dgrad_" + _KEYS[dtype]] += 1
     with torch.cuda.device(gy.device):
+        if dtype in HALF_DTYPES:
+            img = packed_weight(weight, "bwd", dtype)
+            _lib.check(lib.mrp_compress_bwd_data_t(HALF_DTYPES[dtype], _ptr(gy), gs, n, C, H * W, _ptr(img), _ptr(gx),
+                                                   gxs, _ptr(ga), gas, st), "mrp_compress_bwd_data_t")
+            return gx, ga
         if _split("dgrad"):
             img = packed_weight(weight, "bwd")
             _lib.check(lib.mrp_compress_bwd_data_split(_ptr(gy), gs, n, C, H * W, _ptr(img), _ptr(gx), gxs, _ptr(ga),
@@ -205,6 +275,11 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
     from .dist import grad_out_like, release_grad_out
     n, C, H, W = gy.shape
     lib = _lib.load_library()
+    dtype = x.dtype  # the feature dtype: gy and a are cast to it; dW and db are fp32 either way
+    if gy.dtype != dtype:
+        gy = gy.to(dtype)
+    if a.dtype != dtype:
+        a = a.to(dtype)
     gy, gs = _node_major(gy)
     x, xs = _node_major(x)
     a, as_ = _node_major(a)
@@ -223,7 +298,11 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
             db = torch.empty((C,), device=gy.device, dtype=torch.float32)
     P = H * W
     split = _split("wgrad") and C % 64 == 0 and P % 32 == 0
-    if split:
+    if dtype in HALF_DTYPES:
+        nbytes = int(lib.mrp_compress_bwd_weight_t_workspace(n, C, P))
+        typed = lib.mrp_compress_bwd_weight_t
+        fn, name = (lambda *args: typed(HALF_DTYPES[dtype], *args)), "mrp_compress_bwd_weight_t"
+    elif split:
         nbytes = int(lib.mrp_compress_bwd_weight_split_workspace(n, C, P))
         fn, name = lib.mrp_compress_bwd_weight_split, "mrp_compress_bwd_weight_split"
     else:
@@ -238,6 +317,7 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
         if code == _lib.HIP_ERROR_NOT_SUPPORTED:
             return None
         _lib.check(code, name)
+        PATH_COUNTS["wgrad_" + _KEYS[dtype]] += 1
         done = True
         return dw, db
     finally:
@@ -272,7 +352,8 @@ def _lib_backward_weight(gy, x, a, want_bias):
 
 
 # ---- shapes the kernels do not tile: the same kernels on zero-padded operands ---------------------
-# C rounded up to 32 and H W to 4 (forward, data gradient) or 32 (weight gradient): padded channels
+# C rounded up to 32 and H W to 4 — 8 for bf16 / fp16 features — (forward, data gradient) or 32 (weight
+# gradient): padded channels
 # carry zero features and zero weight rows / columns, padded pixels zero features and zero gradients,
 # so every padded term of every sum is a product with an exact zero and the results are the leading
 # blocks of the padded ones.
@@ -310,7 +391,7 @@ def _padded_params(weight: torch.Tensor, bias):
 def _pad_planes(t: torch.Tensor, Cp: int, Pp: int) -> torch.Tensor:
     """(N, C, H, W) -> (N, Cp, Pp, 1) with t in the leading (C, H W) block, zeros elsewhere."""
     n, C, H, W = t.shape
-    out = torch.zeros((n, Cp, Pp, 1), device=t.device, dtype=torch.float32)
+    out = torch.zeros((n, Cp, Pp, 1), device=t.device, dtype=t.dtype)
     out.view(n, Cp, Pp)[:, :C, : H * W] = t.reshape(n, C, H * W)
     return out
 
@@ -322,32 +403,33 @@ def _unpad_planes(t: torch.Tensor, C: int, H: int, W: int) -> torch.Tensor:
 
 def _fwd(weight, bias, x, a):
     n, C, H, W = x.shape
-    if kernels_supported(C, H * W):
+    if kernels_supported(C, H * W, x.dtype):
         return compress_forward(weight, bias, x, a)
-    Cp, Pp = _round(C, 32), _round(H * W, 4)
+    Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(x.dtype))
     wp, bp = _padded_params(weight, bias)
-    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a, Cp, Pp))
+    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a.to(x.dtype), Cp, Pp))
     return _unpad_planes(y, C, H, W)
 
 
-def _bwd_data(weight, gy):
+def _bwd_data(weight, gy, dtype=None):
     n, C, H, W = gy.shape
-    if kernels_supported(C, H * W):
-        return compress_backward_data(weight, gy)
-    Cp, Pp = _round(C, 32), _round(H * W, 4)
+    dtype = gy.dtype if dtype is None else dtype
+    if kernels_supported(C, H * W, dtype):
+        return compress_backward_data(weight, gy, dtype=dtype)
+    Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(dtype))
     wp, _ = _padded_params(weight, None)
-    gx, ga = compress_backward_data(wp, _pad_planes(gy, Cp, Pp))
+    gx, ga = compress_backward_data(wp, _pad_planes(gy.to(dtype), Cp, Pp))
     return _unpad_planes(gx, C, H, W), _unpad_planes(ga, C, H, W)
 
 
 def _bwd_weight(gy, x, a, want_bias, weight, bias, want_weight=True):
     n, C, H, W = gy.shape
-    if kernels_supported(C, H * W):
+    if kernels_supported(C, H * W, x.dtype):
         r = compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight)
         if r is not None:
             return r
     Cp, Pp = _round(C, 32), _round(H * W, 32)
-    r = compress_backward_weight(*(_pad_planes(t, Cp, Pp) for t in (gy, x, a)), want_bias)
+    r = compress_backward_weight(*(_pad_planes(t.to(x.dtype), Cp, Pp) for t in (gy, x, a)), want_bias)
     if r is None:
         raise RuntimeError(f"mrp_gnn: the compress weight-gradient kernels declined the padded shape C={Cp}, HW={Pp}")
     dwp, dbp = r
@@ -371,7 +453,7 @@ class CompressFunction(torch.autograd.Function):
         x, a, weight = ctx.saved_tensors
         gx = ga = dw = db = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gx, ga = _bwd_data(weight, gy) if ctx.hip else _lib_backward_data(weight, gy)
+            gx, ga = _bwd_data(weight, gy, x.dtype) if ctx.hip else _lib_backward_data(weight, gy)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             dw, db = _bwd_weight(gy, x, a, ctx.has_bias, None, None) if ctx.hip else \
                 _lib_backward_weight(gy, x, a, ctx.has_bias)
@@ -417,7 +499,11 @@ def compress_1x1(conv: torch.nn.Conv2d, h: torch.Tensor) -> torch.Tensor:
     matrix-core kernels read its two halves in place (``set_compress_path('library')``: torch's
     library GEMMs)."""
     C = h.shape[1] // 2
-    if not h.is_cuda or h.dtype != torch.float32 or h.shape[1] != 2 * C or not conv_is_plain_1x1(conv, C):
+    half = h.dtype in HALF_DTYPES
+    native = h.dtype == torch.float32 or (half and _HALF[0] == "native" and _PATH[0] != "library")
+    if not h.is_cuda or not native or h.shape[1] != 2 * C or not conv_is_plain_1x1(conv, C):
+        if half and h.is_cuda:
+            PATH_COUNTS["torch_16"] += 1
         return conv(h)
     if _PATH[0] == "library":
         return LibraryCompressFunction.apply(h, conv.weight, conv.bias)
@@ -436,7 +522,7 @@ class FilmCompressFunction(torch.autograd.Function):
     def forward(ctx, x, gb, weight, bias, csr, mode: int):
         from .aggregate import film_mean_forward_into
         n, C, H, W = x.shape
-        agg = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        agg = torch.empty(x.shape, device=x.device, dtype=x.dtype)
         film_mean_forward_into(x, gb, csr, mode, agg)
         hip = _PATH[0] != "library"
         y = _fwd(weight, bias, x, agg) if hip else _lib_forward(weight, bias, x, agg)
@@ -451,7 +537,7 @@ class FilmCompressFunction(torch.autograd.Function):
         need_x, need_gb = ctx.needs_input_grad[0], gb is not None and ctx.needs_input_grad[1]
         dx = dgb = dw = db = None
         if need_x or need_gb:
-            gx, ga = _bwd_data(weight, gy) if ctx.hip else _lib_backward_data(weight, gy)
+            gx, ga = _bwd_data(weight, gy, x.dtype) if ctx.hip else _lib_backward_data(weight, gy)
             dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                          grad_x_base=gx if need_x else None)
             if dgb is not None:
@@ -466,11 +552,13 @@ class FilmCompressFunction(torch.autograd.Function):
 
 
 def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
-    """Whether :func:`film_compress` takes this layer: fp32 CUDA (N, C, H, W) features and a plain 1x1
-    ``Conv2d(2C, C)`` (the matrix-core kernels, or torch's GEMMs for shapes they decline).  bf16 / fp16
-    features are declined: their layer is the 16-bit cat kernel followed by ``conv(h)``, torch's own
-    convolution (under ``torch.autocast`` with fp32 weights); a native 16-bit compress does not exist."""
-    return x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv_is_plain_1x1(conv, x.shape[1])
+    """Whether :func:`film_compress` takes this layer: fp32, bf16 or fp16 CUDA (N, C, H, W) features and
+    a plain 1x1 ``Conv2d(2C, C)`` with fp32 parameters (the matrix-core kernels, on zero-padded operands
+    for shapes they do not tile), inside or outside ``torch.autocast``.  Declined, i.e. left to the cat
+    kernel followed by ``conv(h)``: a conv whose weight is stored in 16 bits (a module cast with
+    ``.to(torch.bfloat16)``), and 16-bit features after ``set_half_compress("torch")``."""
+    ok = x.dtype == torch.float32 or (x.dtype in HALF_DTYPES and _HALF[0] == "native")
+    return x.dim() == 4 and x.is_cuda and ok and conv_is_plain_1x1(conv, x.shape[1])
 
 
 def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int) -> torch.Tensor:

@@ -66,6 +66,8 @@ int mrp_tuning_set(const char* name, int32_t value) {
       {"enc_bwd_psa", &t.enc_bwd_psa, 0, 2},
       {"enc_s1", &t.enc_s1, 0, 64},
       {"enc_s2", &t.enc_s2, 0, 64},
+      {"compress_half", &t.compress_half, 0, 1},
+      {"half_nt_splits", &t.half_nt_splits, 0, 256},
   };
   for (const Knob& k : knobs) {
     if (std::strcmp(name, k.name) == 0) {

@@ -57,6 +57,10 @@ struct Tuning {
   // pre-split (W2^T's image; dz^T written as an image by dzT_pack), 1 = only W2^T's, 0 = neither
   int enc_bwd_psa = 2;
   int enc_s1 = 0, enc_s2 = 0;  // mrp_edge_encoder_bwd_fused: split counts of its two products (0: planner)
+  // the bf16 / fp16 compress (compress_half.hip): 0 = its entry points decline every shape (A/B runs);
+  // the weight gradient's split-K count (0: compress_split.hip's planner)
+  int compress_half = 1;
+  int half_nt_splits = 0;
 };
 Tuning& tuning();
 

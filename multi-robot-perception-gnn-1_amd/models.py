@@ -168,7 +168,11 @@ class GCN(_PackedImages, nn.Module):
         gradient half and the aggregate's gradient straight into the aggregation backward, plus the
         split-K weight-gradient kernel (``compress.FilmCompressFunction``).  With
         ``compress.set_compress_path('library')``: the cat kernel + torch's library GEMMs.  bf16 / fp16
-        features (a backbone under ``torch.autocast``): the 16-bit cat kernel, then ``conv(h)`` by torch."""
+        features with fp32 conv parameters (a backbone under ``torch.autocast``, or outside it) take the
+        same route on the 16-bit kernels (``compress_half.hip``) and return their dtype: the weight
+        rounded once to it, fp32 accumulation and bias, one rounding at the store, fp32 ``dW`` / ``db``.
+        A conv stored in 16 bits, or ``compress.set_half_compress('torch')``: the 16-bit cat kernel,
+        then ``conv(h)`` by torch."""
         x = feats
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):

@@ -267,6 +267,86 @@ int64_t mrp_film_mean_bwd_workspace(int32_t num_graphs, int32_t max_nodes, int32
                                     int32_t C, int32_t P);
 
 /*
+ * The aggregation on pixel-major ("channels-last") feature maps: what a backbone run with
+ * memory_format=torch.channels_last hands over.  Node v's pixel p (P = H*W pixels) is a row of C
+ * contiguous elements of `dtype` at
+ *
+ *     base + v * node_stride + p * pixel_stride          (strides in elements of `dtype`)
+ *
+ * with pixel_stride >= C (C for a dense channels-last tensor, 2C for either half of a channels-last
+ * concatenation buffer) and node_stride >= P * pixel_stride.  Every feature tensor of these entry
+ * points (x, out, grad_out, grad_x, grad_x_base, the epilogue's x0 and xcopy) is such a
+ * (pointer, node_stride, pixel_stride) triple; each may have its own strides.  gb / grad_gb, the
+ * graph arguments, C, P and mode are those of mrp_film_mean_fwd_t / mrp_film_mean_bwd_t.
+ *
+ * The arithmetic is the node-major entry points', operation for operation, so for every graph, mode,
+ * epilogue and dtype
+ *     mrp_film_mean_fwd_cl(x_cl) == mrp_film_mean_fwd_t(x_nchw)           as values, bit for bit,
+ * and grad_x is the fmaf chain of the node-major backward for graphs of <= 8 nodes (base or 0, then
+ * self_scale * G[u], then Wt[u][v] * G[v] for v ascending): bit-equal to it there.  grad_gb is summed
+ * over the pixels in a fixed order of its own (deterministic; no atomics; every output element is
+ * written by one lane).
+ *
+ * Return codes: hipErrorInvalidValue for an unknown dtype, a NULL pointer with work to do,
+ * pixel_stride < C, node_stride < P * pixel_stride, max_nodes > MRP_MAX_NODES or a workspace smaller
+ * than the query; hipErrorNotSupported when P * pixel_stride * sizeof(dtype) of a tensor reaches 2^31
+ * (the kernels' per-lane byte offsets are 32 bits) or the launch grid would exceed 2^31 - 1
+ * workgroups (the LDS tiles always fit: the channel block shrinks with the slot count); both are
+ * decided on the host before anything is enqueued.  Zero sizes succeed without a launch.  No host
+ * synchronisation: the entry points can be captured into a graph.
+ *
+ * Lanes access 16-byte channel vectors when every pointer is 16-byte aligned, C * sizeof(dtype) is a
+ * multiple of 16 and every node and pixel stride is a multiple of 16 bytes; otherwise the same kernel
+ * template runs with one element per access.
+ */
+typedef struct mrp_agg_epilogue_cl {
+    float agg_scale;
+    float self_scale;
+    const void* x0;
+    int64_t x0_node_stride;
+    float x0_scale;
+    void* xcopy;
+    int64_t xcopy_node_stride;
+    int64_t x0_pixel_stride;
+    int64_t xcopy_pixel_stride;
+} mrp_agg_epilogue_cl; /* mrp_agg_epilogue plus the two pixel strides */
+
+int mrp_film_mean_fwd_cl(int32_t dtype,
+                         const void* x, int64_t x_node_stride, int64_t x_pixel_stride,
+                         const float* gb,
+                         const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                         const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                         int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                         int32_t C, int32_t P, int32_t mode,
+                         void* out, int64_t out_node_stride, int64_t out_pixel_stride,
+                         const mrp_agg_epilogue_cl* epilogue,
+                         void* stream);
+
+/* Backward of mrp_film_mean_fwd_cl (see mrp_film_mean_bwd for the formulas; grad_x and grad_gb may
+ * each be NULL; COPY_MEAN zero-fills grad_gb; x is read only when grad_gb is wanted).  The Gram of a
+ * plane split over several workgroups is summed through `workspace` (>= the query's bytes, 4-byte
+ * aligned; NULL / 0 allowed when the query returns 0) in segment order by a second launch. */
+int mrp_film_mean_bwd_cl(int32_t dtype,
+                         const void* grad_out, int64_t g_node_stride, int64_t g_pixel_stride,
+                         const void* x, int64_t x_node_stride, int64_t x_pixel_stride,
+                         const float* gb,
+                         const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                         const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                         int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                         int32_t C, int32_t P, int32_t mode,
+                         void* grad_x, int64_t gx_node_stride, int64_t gx_pixel_stride,
+                         const void* grad_x_base, int64_t base_node_stride, int64_t base_pixel_stride,
+                         float* grad_gb,
+                         const mrp_agg_epilogue_cl* epilogue,
+                         void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* Bytes of workspace mrp_film_mean_bwd_cl needs for these sizes (the same for every dtype); 0 when
+ * grad_gb is not wanted (want_grad_gb == 0), for COPY_MEAN, and when no plane is split. */
+int64_t mrp_film_mean_bwd_cl_workspace(int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                       int32_t C, int32_t P, int32_t mode, int32_t want_grad_gb);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

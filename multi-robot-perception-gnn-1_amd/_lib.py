@@ -27,6 +27,9 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_fwd_t",
     "mrp_film_mean_bwd_t",
     "mrp_film_mean_bwd_workspace",
+    "mrp_film_mean_fwd_cl",
+    "mrp_film_mean_bwd_cl",
+    "mrp_film_mean_bwd_cl_workspace",
     "mrp_compress_fwd",
     "mrp_compress_weight_transpose",
     "mrp_compress_bwd_data",
@@ -101,6 +104,12 @@ class Epilogue(ctypes.Structure):
                 ("xcopy_node_stride", ctypes.c_int64)]
 
 
+class EpilogueCl(ctypes.Structure):
+    """``mrp_agg_epilogue_cl``: ``Epilogue`` plus the pixel strides of x0 and xcopy (pixel-major tensors)."""
+
+    _fields_ = Epilogue._fields_ + [("x0_pixel_stride", ctypes.c_int64), ("xcopy_pixel_stride", ctypes.c_int64)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -128,6 +137,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_mean_bwd_t.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32]
     lib.mrp_film_mean_bwd_workspace.restype = ctypes.c_int64
+    epc = ctypes.POINTER(EpilogueCl)
+    lib.mrp_film_mean_fwd_cl.argtypes = [_I32, _P, _I64, _I64, _P] + graph + [_P, _I64, _I64, epc, _P]
+    lib.mrp_film_mean_fwd_cl.restype = ctypes.c_int
+    lib.mrp_film_mean_bwd_cl.argtypes = ([_I32, _P, _I64, _I64, _P, _I64, _I64, _P] + graph +
+                                         [_P, _I64, _I64, _P, _I64, _I64, _P, epc, _P, _I64, _P])
+    lib.mrp_film_mean_bwd_cl.restype = ctypes.c_int
+    lib.mrp_film_mean_bwd_cl_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32, _I32, _I32]
+    lib.mrp_film_mean_bwd_cl_workspace.restype = ctypes.c_int64
     lib.mrp_tuning_set.argtypes = [ctypes.c_char_p, _I32]
     lib.mrp_tuning_set.restype = ctypes.c_int
     lib.mrp_compress_fwd.argtypes = [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]

@@ -8,6 +8,10 @@ Reference semantics (``dgl/model/models.py:207-211,223``)::
 ``gb`` is the edge encoder's sigmoid output viewed ``(E, C, 2)`` (gamma = ``[..., 0]``,
 beta = ``[..., 1]``, ``models.py:154-155``) and is read in place, never split or copied.
 
+Feature maps are taken in either layout: NCHW (a contiguous C*H*W block per node) or pixel-major
+``torch.channels_last`` (``pixel_strides``), each with kernels of its own and the same arithmetic; a
+channels_last input gives a channels_last output with no conversion (``set_channels_last``).
+
 Everything here dispatches to the HIP library through its C ABI; a CPU tensor raises.
 """
 from __future__ import annotations
@@ -56,6 +60,67 @@ def _as_node_major(t: torch.Tensor):
         t = t.contiguous()
         s = t.shape[1] * t.shape[2] * t.shape[3]
     return t, s
+
+
+#: How a pixel-major (channels_last) feature map is aggregated: "native" runs the pixel-major kernels
+#: (``mrp_film_mean_fwd_cl`` / ``_bwd_cl``) and returns channels_last; "convert" copies it to NCHW first
+#: and runs the node-major kernels (the route before the pixel-major kernels existed; for A/B runs).
+_CHANNELS_LAST = "native"
+
+
+def set_channels_last(mode: str) -> str:
+    """Select the route of channels_last inputs ("native" or "convert"); returns the previous setting."""
+    global _CHANNELS_LAST
+    if mode not in ("native", "convert"):
+        raise ValueError(f'channels_last route must be "native" or "convert", got {mode!r}')
+    prev, _CHANNELS_LAST = _CHANNELS_LAST, mode
+    return prev
+
+
+def pixel_strides(t: torch.Tensor):
+    """(node_stride, pixel_stride) in elements of a pixel-major (N, C, H, W) fp32 / bf16 / fp16 tensor —
+    every pixel a row of C contiguous channels, the rows of a node ``pixel_stride >= C`` apart in (h, w)
+    order: ``torch.channels_last`` tensors (pixel stride C) and channel slices of them, such as either
+    half of a channels_last concatenation buffer (pixel stride 2C) — else None.  Node-major wins every
+    ambiguous case: a tensor ``node_stride`` accepts, C == 1 or H*W == 1 give None."""
+    if t.dim() != 4 or t.dtype not in FEATURE_DTYPES:
+        return None
+    n, c, h, w = t.shape
+    if n == 0 or c <= 1 or h * w <= 1 or node_stride(t) is not None:
+        return None
+    s = t.stride()
+    if s[1] != 1:
+        return None
+    ps = s[3] if w > 1 else s[2]
+    if ps < c or (w > 1 and h > 1 and s[2] != w * ps):
+        return None
+    if n > 1 and s[0] < h * w * ps:
+        return None
+    return (s[0] if n > 1 else h * w * ps), ps
+
+
+def _as_pixel_major(t: torch.Tensor):
+    """(tensor, node_stride, pixel_stride), converting (one copy) a tensor that is not pixel-major."""
+    s = pixel_strides(t)
+    if s is None:
+        t = t.contiguous(memory_format=torch.channels_last)
+        s = pixel_strides(t)
+        if s is None:  # C == 1 or H*W == 1: both layouts at once; the dense strides describe it
+            n, c, h, w = t.shape
+            s = (c * h * w, c)
+    return t, s[0], s[1]
+
+
+def _native_cl(t: torch.Tensor) -> bool:
+    return _CHANNELS_LAST == "native" and pixel_strides(t) is not None
+
+
+def _empty_like_layout(x: torch.Tensor, shape=None) -> torch.Tensor:
+    """An output for x: dense channels_last when x takes the pixel-major kernels, else NCHW-contiguous."""
+    shape = tuple(x.shape) if shape is None else shape
+    if _native_cl(x):
+        return torch.empty(shape, device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    return torch.empty(shape, device=x.device, dtype=x.dtype)
 
 
 def _require_device(*ts):
@@ -131,8 +196,67 @@ def _epilogue_struct(ep: Optional[EpilogueSpec], shape, dtype=torch.float32):
     return st, keep
 
 
+def _gb_fp32(gb, csr, C, mode):
+    if (mode & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN:
+        return None
+    if gb is None:
+        raise ValueError("gamma/beta tensor required for FiLM modes")
+    gb = gb.reshape(csr.num_edges, C, 2)
+    if not gb.is_contiguous() or gb.dtype != torch.float32:
+        gb = gb.contiguous().float()
+    _require_device(gb)
+    return gb
+
+
+def _graph_args(gb, csr, C, P, mode):
+    return (_ptr(gb), _ptr(csr.indptr), _ptr(csr.src), _ptr(csr.eid), _ptr(csr.graph_off),
+            csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes, csr.num_edges, C, P, mode)
+
+
+def _forward_cl(x, gb, csr, mode, out, epilogue=None):
+    """The forward on pixel-major tensors (``mrp_film_mean_fwd_cl``); ``out`` is pixel-major, x (and the
+    epilogue's x0) are converted to that layout if they are not."""
+    n, C, H, W = x.shape
+    if tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype}")
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    x, xs, xp = _as_pixel_major(x)
+    os_, op = pixel_strides(out)
+    gb = _gb_fp32(gb, csr, C, mode)
+    ep, keep = None, []
+    if epilogue is not None and not epilogue.is_plain():
+        x0p = x0s = x0ps = xcp = xcs = xcps = 0
+        if epilogue.x0 is not None:
+            if tuple(epilogue.x0.shape) != (n, C, H, W):
+                raise ValueError(f"x0 must have the node features' shape {(n, C, H, W)}")
+            _require_device(epilogue.x0)
+            x0, x0s, x0ps = _as_pixel_major(epilogue.x0.to(x.dtype) if epilogue.x0.dtype != x.dtype else epilogue.x0)
+            keep.append(x0)
+            x0p = x0.data_ptr()
+        if epilogue.xcopy is not None:
+            xc = epilogue.xcopy
+            st = pixel_strides(xc)
+            if st is None or tuple(xc.shape) != (n, C, H, W) or xc.dtype != x.dtype:
+                raise ValueError("xcopy must be a pixel-major (N, C, H, W) tensor in x's dtype")
+            _require_device(xc)
+            xcp, (xcs, xcps) = xc.data_ptr(), st
+        ep = _lib.EpilogueCl(epilogue.agg_scale, epilogue.self_scale, x0p, x0s, epilogue.x0_scale, xcp, xcs,
+                             x0ps, xcps)
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_mean_fwd_cl(FEATURE_DTYPES[x.dtype], _ptr(x), xs, xp, *_graph_args(gb, csr, C, H * W, mode),
+                                        _ptr(out), os_, op, ctypes.byref(ep) if ep is not None else None,
+                                        _stream(x.device))
+    _lib.check(code, "mrp_film_mean_fwd_cl")
+    PATH_COUNTS["fwd_cl_" + _DTYPE_KEYS[x.dtype]] += 1
+    return out
+
+
 def _forward(x, gb, csr, mode, out, epilogue=None):
     _require_device(x, out)
+    if _native_cl(out):  # x follows out's layout family
+        return _forward_cl(x, gb, csr, mode, out, epilogue)
     n, C, H, W = x.shape
     x, xs = _as_node_major(x)
     os_ = node_stride(out)
@@ -168,11 +292,15 @@ def _forward(x, gb, csr, mode, out, epilogue=None):
 
 def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR,
                        mode: int, need_dx: bool, need_dgb: bool, grad_x_base: Optional[torch.Tensor] = None,
-                       epilogue: Optional[EpilogueSpec] = None):
+                       epilogue: Optional[EpilogueSpec] = None, pixel_major: bool = True):
     """(grad_x or None, grad_gb (E, C, 2) or None) for the forward above; ``grad_x_base`` (N, C, H, W),
     if given, is added into grad_x by the kernel.  ``epilogue``: the forward's (its agg_scale and
-    self_scale enter here; the gradient of x0 is x0_scale * grad_out, formed by the caller)."""
+    self_scale enter here; the gradient of x0 is x0_scale * grad_out, formed by the caller).
+    A pixel-major (channels_last) x takes the pixel-major kernels and gives a channels_last grad_x,
+    unless ``pixel_major=False`` (a caller whose forward ran the NCHW kernels on a converted x)."""
     _require_device(grad_out, x)
+    if pixel_major and _native_cl(x):
+        return _backward_cl(grad_out, x, gb, csr, mode, need_dx, need_dgb, grad_x_base, epilogue)
     n, C, H, W = x.shape
     dtype = x.dtype  # the feature dtype: grad_out and the base are cast to it, grad_x is allocated in it
     if grad_out.dtype != dtype:
@@ -220,6 +348,48 @@ def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[tor
     return dx, dgb
 
 
+def _backward_cl(grad_out, x, gb, csr, mode, need_dx, need_dgb, grad_x_base, epilogue):
+    """``film_mean_backward`` for a pixel-major x (``mrp_film_mean_bwd_cl``): grad_out and the base are
+    cast to x's dtype and converted (once) to its layout if they arrive otherwise; grad_x is dense
+    channels_last."""
+    n, C, H, W = x.shape
+    dtype = x.dtype
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
+    grad_out, gs, gp = _as_pixel_major(grad_out)
+    base, bs, bp = None, 0, 0
+    if grad_x_base is not None and need_dx:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
+        base, bs, bp = _as_pixel_major(grad_x_base)
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype, memory_format=torch.channels_last) if need_dx else None
+    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    xs, xp = pixel_strides(x)
+    dxs, dxp = pixel_strides(dx) if dx is not None else (0, 0)
+    if gb is not None:
+        gb = gb.reshape(csr.num_edges, C, 2)
+        if not gb.is_contiguous() or gb.dtype != torch.float32:
+            gb = gb.contiguous().float()
+    ep = None
+    if epilogue is not None and (epilogue.agg_scale != 1.0 or epilogue.self_scale != 0.0):
+        ep = _lib.EpilogueCl(epilogue.agg_scale, epilogue.self_scale, 0, 0, 0.0, 0, 0, 0, 0)
+    lib = _lib.load_library()
+    ws, nbytes = None, 0
+    if need_dgb:  # partial Gram sums of a split plane (the library never allocates)
+        nbytes = int(lib.mrp_film_mean_bwd_cl_workspace(csr.num_graphs, csr.max_nodes, csr.graph_kind, C, H * W,
+                                                        mode, 1))
+        if nbytes > 0:
+            ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_mean_bwd_cl(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, gp, _ptr(x), xs, xp,
+                                        *_graph_args(gb, csr, C, H * W, mode), _ptr(dx), dxs, dxp,
+                                        _ptr(base), bs, bp, _ptr(dgb), ctypes.byref(ep) if ep is not None else None,
+                                        _ptr(ws), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_mean_bwd_cl")
+    PATH_COUNTS["bwd_cl_" + _DTYPE_KEYS[dtype]] += 1
+    return dx, dgb
+
+
 class FilmMeanFunction(torch.autograd.Function):
     """Autograd wrapper: forward = ``mrp_film_mean_fwd_ex``, backward = ``mrp_film_mean_bwd_ex``.
     ``mode`` may carry ``_lib.GB_LOGITS`` (gb = pre-sigmoid logits; the gradient is then d logits).
@@ -227,7 +397,7 @@ class FilmMeanFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gb, x0, csr: GraphCSR, mode: int, scales=(1.0, 0.0, 0.0)):
-        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+        out = _empty_like_layout(x)  # channels_last for a channels_last x
         ep = EpilogueSpec(scales[0], scales[1], x0, scales[2])
         film_mean_forward_into(x, gb, csr, mode, out, epilogue=ep)
         ctx.save_for_backward(x, gb)
@@ -315,7 +485,7 @@ class FilmMeanCatFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gb, csr: GraphCSR, mode: int):
         n, C, H, W = x.shape
-        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        buf = _empty_like_layout(x, (n, 2 * C, H, W))  # channels_last x: halves with pixel stride 2C
         film_mean_cat_forward_into(x, gb, csr, mode, buf)  # the kernel also writes x into buf[:, :C]
         ctx.save_for_backward(x, gb)
         ctx.csr = csr

@@ -539,7 +539,8 @@ class FilmCompressFunction(torch.autograd.Function):
         if need_x or need_gb:
             gx, ga = _bwd_data(weight, gy, x.dtype) if ctx.hip else _lib_backward_data(weight, gy)
             dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
-                                         grad_x_base=gx if need_x else None)
+                                         grad_x_base=gx if need_x else None,
+                                         pixel_major=False)  # the forward above ran the NCHW kernels
             if dgb is not None:
                 dgb = dgb.view(gb.shape).to(gb.dtype)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):

@@ -16,7 +16,8 @@
 // Kernel family (template Cfg<MF, BK, NBUF, WM, WN>): a workgroup of WM x WN waves owns a
 // (64 WM) x (64 WN) output tile, each wave 64 x 64, accumulated over K stages of BK on fp32 MFMAs
 // (MF = 16: v_mfma_f32_16x16x4_f32, 4 x 4 blocks per wave; MF = 32: v_mfma_f32_32x32x2_f32, 2 x 2
-// blocks) — f32 in, f32 accumulate: exact fp32 products, an fmaf chain per output.  Operands are
+// blocks) — f32 in, f32 accumulate: exact fp32 products, an fmaf chain per output (gemm_nn: chains of
+// at most kFlushK = 128 terms, their sums added in k order).  Operands are
 // staged HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: no VGPRs, one instruction per KiB) into
 // NBUF LDS buffers, NBUF - 1 stages in flight while one is multiplied.  The LDS images are
 // lane-linear (what LDS-DMA writes); the bank swizzle is applied to the per-lane SOURCE address
@@ -269,6 +270,8 @@ struct NNArgs {
   int32_t M, K, k0, m0, P, mtiles;
 };
 
+constexpr int kFlushK = 128;  // longest fmaf chain of gemm_nn (a multiple of 16, the k of one mma group)
+
 template <class G>
 __global__ void __launch_bounds__(G::THREADS, G::WG_PER_CU) gemm_nn(NNArgs a) {
   using AC = Acc<G::MF>;
@@ -345,8 +348,41 @@ __global__ void __launch_bounds__(G::THREADS, G::WG_PER_CU) gemm_nn(NNArgs a) {
 #pragma unroll
     for (int nb = 0; nb < G::FB; ++nb) read_bnn<G>(Bs, boff, g, nb, fr[1][nb]);
   };
-  auto mma = [&](const float (&fr)[2][G::FB][G::T]) { mma_group<G>(acc, fr[0], fr[1]); };
+  // The fmaf chain of an output is cut every kFlushK terms: the running chain is added into a second
+  // accumulator and restarts from 0, so no chain is longer than kFlushK (one chain over K = 1024 measured
+  // 2.6 x the error of torch's fp32 GEMM against float64, tests/test_gpu_split_fp32.py; K <= kFlushK is
+  // the single chain, bit for bit).
+  typename AC::T tot[G::FB][G::FB];
+#pragma unroll
+  for (int mb = 0; mb < G::FB; ++mb)
+#pragma unroll
+    for (int nb = 0; nb < G::FB; ++nb)
+#pragma unroll
+      for (int r = 0; r < AC::R; ++r) tot[mb][nb][r] = 0.f;
+  constexpr int kFlushGroups = kFlushK / 16;
+  int ngroups = 0;
+  auto mma = [&](const float (&fr)[2][G::FB][G::T]) {
+    mma_group<G>(acc, fr[0], fr[1]);
+    if (++ngroups == kFlushGroups) {
+      ngroups = 0;
+#pragma unroll
+      for (int mb = 0; mb < G::FB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < G::FB; ++nb)
+#pragma unroll
+          for (int r = 0; r < AC::R; ++r) {
+            tot[mb][nb][r] = __fadd_rn(tot[mb][nb][r], acc[mb][nb][r]);
+            acc[mb][nb][r] = 0.f;
+          }
+    }
+  };
   kloop<G>(a.K / G::BK, issue, read, mma);
+#pragma unroll
+  for (int mb = 0; mb < G::FB; ++mb)
+#pragma unroll
+    for (int nb = 0; nb < G::FB; ++nb)
+#pragma unroll
+      for (int r = 0; r < AC::R; ++r) acc[mb][nb][r] = __fadd_rn(tot[mb][nb][r], acc[mb][nb][r]);
 
   // ---- epilogue: accumulator (row, col) of each block, + bias, to the row's destination
 #pragma unroll

@@ -61,7 +61,7 @@ __device__ __forceinline__ u4 as_u4(bf8 v) { return __builtin_bit_cast(u4, v); }
 // and the five small products (at most 2^-8 of the product) in a second one, summed once in the
 // epilogue: the long accumulation then sees a sixth of the additions into the large sum, as in the
 // compress GEMMs (compress_split.hip, Acc2), whose pixel sums drifted 6x the fp32 GEMM's error with
-// one accumulator (tests/test_gpu_encoder.py checks the column sums of z at C = 2048).
+// one accumulator (tests/test_gpu_eval_path.py checks the column sums of z at C = 2048).
 __device__ __forceinline__ void mma6_2(const bf8 (&a)[3], const bf8 (&b)[3], f16v& hi, f16v& lo) {
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], lo, 0, 0, 0);
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], lo, 0, 0, 0);

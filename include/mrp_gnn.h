@@ -457,6 +457,51 @@ int mrp_compress_bwd_weight_t(int32_t dtype, const void* gy, int64_t gy_node_str
                               int64_t workspace_bytes, void* stream);
 
 /*
+ * The same three products on pixel-major (torch.channels_last) bf16 / fp16 feature maps
+ * (compress_half_cl.hip).  Every feature tensor is a (pointer, node stride, pixel stride) triple in
+ * elements, as the _cl aggregation entry points define it: pixel p of node n is C contiguous channels at
+ * n * node_stride + p * pixel_stride — pixel stride C for a dense channels_last map, 2C for either half
+ * of a channels_last concatenation buffer; node_stride >= P * pixel_stride, not necessarily equal.  The
+ * arithmetic is the _t entry points': the weight rounded once to T when packed (the same
+ * mrp_compress_pack_t images: pack_t(w, 2C, 0, C, 2C) for the forward, pack_t(w, 2C, 1, 2C, C) for the data
+ * gradient), fp32 accumulation, the fp32 bias (may be NULL) added to the fp32 sum, one rounding at the
+ * store; gw (C, 2C) and gbias (C, may be NULL) accumulated and stored in fp32.
+ *   mrp_compress_fwd_cl                  y = T(W_T [x; agg] + bias) per pixel row
+ *   mrp_compress_bwd_data_cl             [gx; gagg] = T(W_T^T gy): two pixel-major outputs with their own
+ *                                        strides (e.g. the halves of one channels_last 2C buffer)
+ *   mrp_compress_bwd_weight_cl           gw = sum gy [x; agg]^T, gbias = sum gy over all num_nodes P pixel
+ *                                        rows, split into fp32 partial tiles in workspace
+ *                                        (mrp_compress_bwd_weight_cl_workspace bytes, 16-byte aligned; 0:
+ *                                        none needed) summed in a fixed order by a second launch: no
+ *                                        atomics, two runs give the same bits
+ * Pixels are rows: any P is tiled (no padding; a stage may cross a node boundary).  Before any launch:
+ * MRP_DTYPE_F32 or an unknown dtype, a NULL pointer with work to do, a pointer that is not 16-byte
+ * aligned, a node or pixel stride that is not a multiple of 8 elements, a pixel stride below C, a node
+ * stride below P pixel strides or a workspace that is too small return hipErrorInvalidValue; zero sizes
+ * return success without a launch (an empty weight-gradient sum zeroes gw / gbias).  C % 32 != 0, a
+ * packed image or a pixel-row count beyond 31 bits — and every shape while the tuning knob
+ * "compress_half_cl" is 0 — return hipErrorNotSupported.  mrp_compress_bwd_weight_cl needs gw whenever
+ * it has work to do (gbias alone is not computed: gw == NULL with gbias != NULL is hipErrorInvalidValue;
+ * both NULL is a no-op).  The knob is for callers of this C interface: compress.py does not consult it
+ * (its own switch is compress.set_channels_last_compress) and raises on a declined pixel-major call.  No
+ * host synchronisation; stream-capturable.
+ */
+int mrp_compress_fwd_cl(int32_t dtype, const void* x, int64_t x_node_stride, int64_t x_pixel_stride, const void* agg,
+                        int64_t agg_node_stride, int64_t agg_pixel_stride, int32_t num_nodes, int32_t C, int32_t P,
+                        const void* packed_w, const float* bias, void* y, int64_t y_node_stride,
+                        int64_t y_pixel_stride, void* stream);
+int mrp_compress_bwd_data_cl(int32_t dtype, const void* gy, int64_t gy_node_stride, int64_t gy_pixel_stride,
+                             int32_t num_nodes, int32_t C, int32_t P, const void* packed_wt, void* gx,
+                             int64_t gx_node_stride, int64_t gx_pixel_stride, void* gagg, int64_t gagg_node_stride,
+                             int64_t gagg_pixel_stride, void* stream);
+int64_t mrp_compress_bwd_weight_cl_workspace(int32_t num_nodes, int32_t C, int32_t P);
+int mrp_compress_bwd_weight_cl(int32_t dtype, const void* gy, int64_t gy_node_stride, int64_t gy_pixel_stride,
+                               const void* x, int64_t x_node_stride, int64_t x_pixel_stride, const void* agg,
+                               int64_t agg_node_stride, int64_t agg_pixel_stride, int32_t num_nodes, int32_t C,
+                               int32_t P, float* gw, float* gbias, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+
+/*
  * First layer of the edge encoder, dgl/model/models.py:147-148:  h = relu(pose W1^T + b1).
  *   pose (num_edges, 9), w1 (C, 9) (nn.Linear weight layout), b1 (C) -> h (num_edges, C), fp32.
  * The second Linear is mrp_edge_logits_fwd and its Sigmoid is fused into the aggregation
@@ -617,14 +662,19 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * pre-split, dz^T written as a packed image; 1 = only W2^T's image; 0 = both split in the kernel);
  * "enc_s1" / "enc_s2" (its two products' split-K counts, 0 = the planner's); "compress_half" (1
  * default; 0 = the bf16 / fp16 compress entry points decline every shape, for A/B runs);
- * "half_nt_splits" (mrp_compress_bwd_weight_t's split-K count, 0 default = the planner's, 1..256). */
+ * "half_nt_splits" (mrp_compress_bwd_weight_t's split-K count, 0 default = the planner's, 1..256);
+ * "compress_half_cl" (1 default; 0 = the pixel-major compress entry points mrp_compress_*_cl decline
+ * every shape, for A/B runs); "half_cl_splits" (mrp_compress_bwd_weight_cl's split-K count, 0 default =
+ * the planner's, 1..256). */
 int mrp_tuning_set(const char* name, int32_t value);
 
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
  * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature
  * tensors, enum mrp_dtype) and, added since without a new number (nothing existing changed), the
  * typed compress entry points mrp_compress_pack_t_bytes / _pack_t / _fwd_t / _bwd_data_t /
- * _bwd_weight_t_workspace / _bwd_weight_t and the knobs "compress_half" / "half_nt_splits"; 21: v19 plus
+ * _bwd_weight_t_workspace / _bwd_weight_t and the knobs "compress_half" / "half_nt_splits", and their
+ * pixel-major forms mrp_compress_fwd_cl / _bwd_data_cl / _bwd_weight_cl_workspace / _bwd_weight_cl with the
+ * knobs "compress_half_cl" / "half_cl_splits"; 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

@@ -47,6 +47,10 @@ EXPORTED_SYMBOLS = (
     "mrp_compress_bwd_data_t",
     "mrp_compress_bwd_weight_t_workspace",
     "mrp_compress_bwd_weight_t",
+    "mrp_compress_fwd_cl",
+    "mrp_compress_bwd_data_cl",
+    "mrp_compress_bwd_weight_cl_workspace",
+    "mrp_compress_bwd_weight_cl",
     "mrp_edge_hidden_fwd",
     "mrp_edge_logits_fwd",
     "mrp_edge_encoder_pack_bytes",
@@ -181,6 +185,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_compress_bwd_weight_t_workspace.restype = ctypes.c_int64
     lib.mrp_compress_bwd_weight_t.argtypes = [_I32] + lib.mrp_compress_bwd_weight.argtypes
     lib.mrp_compress_bwd_weight_t.restype = ctypes.c_int
+    t3 = [_P, _I64, _I64]  # a pixel-major tensor: pointer, node stride, pixel stride
+    lib.mrp_compress_fwd_cl.argtypes = [_I32] + t3 + t3 + [_I32, _I32, _I32, _P, _P] + t3 + [_P]
+    lib.mrp_compress_fwd_cl.restype = ctypes.c_int
+    lib.mrp_compress_bwd_data_cl.argtypes = [_I32] + t3 + [_I32, _I32, _I32, _P] + t3 + t3 + [_P]
+    lib.mrp_compress_bwd_data_cl.restype = ctypes.c_int
+    lib.mrp_compress_bwd_weight_cl_workspace.argtypes = [_I32, _I32, _I32]
+    lib.mrp_compress_bwd_weight_cl_workspace.restype = ctypes.c_int64
+    lib.mrp_compress_bwd_weight_cl.argtypes = [_I32] + t3 + t3 + t3 + [_I32, _I32, _I32, _P, _P, _P, _I64, _P]
+    lib.mrp_compress_bwd_weight_cl.restype = ctypes.c_int
     lib.mrp_edge_hidden_fwd.argtypes = [_P, _P, _P, _I32, _I32, _P, _P]
     lib.mrp_edge_hidden_fwd.restype = ctypes.c_int
     lib.mrp_edge_logits_fwd.argtypes = [_P, _I32, _I32, _P, _P, _P, _P]

@@ -36,6 +36,14 @@ data gradients are rounded once at the store, and ``dW`` / ``db`` are accumulate
 Their tiles need C % 32 == 0 and H W % 8 == 0 (32 for the weight gradient); other shapes are
 zero-padded as above.  :func:`set_half_compress` ``("torch")`` restores the earlier route (the 16-bit
 cat kernel + torch's convolution) for A/B runs; :data:`PATH_COUNTS` counts the launches per route.
+
+Pixel-major (``torch.channels_last``) bf16 / fp16 feature maps with C % 32 == 0 run the three products
+on kernels of their own (``csrc/compress_half_cl.hip``: ``mrp_compress_fwd_cl`` / ``_bwd_data_cl`` /
+``_bwd_weight_cl``), which read the features in place — dense maps or the halves of a channels_last
+concatenation buffer — tile any H W without padding, reuse the same packed weight images and return
+dense channels_last.  :func:`set_channels_last_compress` ``("convert")`` restores the earlier route (a
+copy to NCHW, the kernels above, NCHW results); fp32 channels_last features and C % 32 != 0 always take
+it (``PATH_COUNTS["convert_cl"]`` counts the 16-bit calls that did).
 """
 from __future__ import annotations
 
@@ -76,6 +84,70 @@ def set_half_compress(route: str) -> str:
 
 def half_compress() -> str:
     return _HALF[0]
+
+
+_CL = ["native"]
+
+
+def set_channels_last_compress(route: str) -> str:
+    """Route of a pixel-major (``torch.channels_last``) bf16 / fp16 operand set: ``"native"`` (default) the
+    pixel-major kernels of ``compress_half_cl.hip`` (``mrp_compress_fwd_cl`` / ``_bwd_data_cl`` /
+    ``_bwd_weight_cl``), which read the features in place and return channels_last; ``"convert"`` copies
+    them to NCHW and runs the node-major kernels (the route before the pixel-major kernels existed; for
+    A/B runs).  ``aggregate.set_channels_last("convert")`` implies ``"convert"`` here.  C % 32 != 0 and fp32
+    features take the convert route either way.  This switch is the A/B lever from Python; the library's
+    tuning knob ``compress_half_cl`` = 0 makes the C entry points decline and is meant for C callers: this
+    module does not consult it, and a declined pixel-major call raises.  Returns the previous value."""
+    if route not in ("native", "convert"):
+        raise ValueError("channels_last compress route must be 'native' or 'convert'")
+    prev, _CL[0] = _CL[0], route
+    return prev
+
+
+def channels_last_compress() -> str:
+    return _CL[0]
+
+
+def _cl_features(t: torch.Tensor) -> bool:
+    """A bf16 / fp16 pixel-major feature map (``aggregate.pixel_strides``)."""
+    from .aggregate import pixel_strides
+    return t.dtype in HALF_DTYPES and t.is_cuda and pixel_strides(t) is not None
+
+
+def _cl_route(t: torch.Tensor) -> bool:
+    """Whether this feature map's products run on the pixel-major kernels."""
+    from . import aggregate
+    return (_CL[0] == "native" and aggregate._CHANNELS_LAST == "native" and _PATH[0] != "library"
+            and t.shape[1] % 32 == 0 and _cl_features(t))
+
+
+def _count_convert(t: torch.Tensor) -> None:
+    if _cl_features(t):
+        PATH_COUNTS["convert_cl"] += 1
+
+
+def _pstrides(t: torch.Tensor):
+    """(node stride, pixel stride) of a pixel-major tensor laid out as the kernels need (16-byte aligned,
+    strides whole 16-byte pieces), else None."""
+    from .aggregate import pixel_strides
+    s = pixel_strides(t)
+    if s is None or s[0] % 8 != 0 or s[1] % 8 != 0 or t.data_ptr() % 16 != 0:
+        return None
+    return s
+
+
+def _pixel_major(t: torch.Tensor):
+    """(tensor, node stride, pixel stride), converting (one copy) an operand that is not pixel-major."""
+    s = _pstrides(t)
+    if s is None:
+        n, c, h, w = t.shape
+        t = _empty_cl(t.shape, t.device, t.dtype).copy_(t)
+        s = (c * h * w, c)
+    return t, s[0], s[1]
+
+
+def _empty_cl(shape, device, dtype) -> torch.Tensor:
+    return torch.empty(tuple(shape), device=device, dtype=dtype, memory_format=torch.channels_last)
 
 
 def _split(op: str) -> bool:
@@ -194,7 +266,8 @@ def kernels_supported(C: int, P: int, dtype: torch.dtype = torch.float32) -> boo
     return C > 0 and P > 0 and C % 32 == 0 and P % _pixel_multiple(dtype) == 0
 
 
-def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tensor,
+                     pixel_major: bool = None) -> torch.Tensor:
     """``conv(torch.cat((x, a), 1))`` for a (C, 2C, 1, 1) weight without the concatenation
     (``mrp_compress_fwd``); x and a are (N, C, H, W), e.g. views of a cat buffer's halves."""
     from .aggregate import _ptr, _stream
@@ -202,6 +275,21 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
     dtype = x.dtype  # the feature dtype: a is cast to it, y is allocated in it
     if a.dtype != dtype:
         a = a.to(dtype)
+    # pixel-major 16-bit features (or the caller's decision): read in place, y dense channels_last
+    if _cl_route(x) if pixel_major is None else pixel_major:
+        x, xn, xp = _pixel_major(x)
+        a, an, ap = _pixel_major(a)
+        b = bias.detach() if bias is not None else None
+        if b is not None and (b.dtype != torch.float32 or not b.is_contiguous()):
+            b = b.float().contiguous()
+        y = _empty_cl((n, C, H, W), x.device, dtype)
+        PATH_COUNTS["fwd_cl_" + _KEYS[dtype]] += 1
+        with torch.cuda.device(x.device):
+            img = packed_weight(weight, "fwd", dtype)
+            _lib.check(_lib.load_library().mrp_compress_fwd_cl(
+                HALF_DTYPES[dtype], _ptr(x), xn, xp, _ptr(a), an, ap, n, C, H * W, _ptr(img), _ptr(b), _ptr(y),
+                C * H * W, C, _stream(x.device)), "mrp_compress_fwd_cl")
+        return y
     x, xs = _node_major(x)
     a, as_ = _node_major(a)
     w = _weight2d(weight)
@@ -227,16 +315,36 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
 
 
 def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor = None, ga: torch.Tensor = None,
-                           dtype: torch.dtype = None):
+                           dtype: torch.dtype = None, pixel_major: bool = None):
     """(gx, ga) = (W[:, :C]^T gy, W[:, C:]^T gy) per node (``mrp_compress_bwd_data``), written into
     the given (N, C, H, W) outputs (e.g. the halves of a cat buffer's gradient) or new tensors.  The
-    feature dtype is the given outputs', else ``dtype``, else gy's; gy is cast to it."""
+    feature dtype is the given outputs', else ``dtype``, else gy's; gy is cast to it.  16-bit pixel-major
+    outputs (or, with none given, a pixel-major gy — or ``pixel_major=True``, the layout of the forward's
+    features) take the pixel-major kernel (``mrp_compress_bwd_data_cl``): new outputs are dense
+    channels_last, a gy in the other layout is converted once."""
     from .aggregate import _ptr, _stream
     n, C, H, W = gy.shape
     lib = _lib.load_library()
     dtype = gx.dtype if gx is not None else ga.dtype if ga is not None else dtype if dtype is not None else gy.dtype
     if gy.dtype != dtype:
         gy = gy.to(dtype)
+    if pixel_major is None:
+        pixel_major = _cl_route(gx if gx is not None else ga if ga is not None else gy)
+    if pixel_major:
+        gy, gn, gp = _pixel_major(gy)
+        gx = _empty_cl((n, C, H, W), gy.device, dtype) if gx is None else gx
+        ga = _empty_cl((n, C, H, W), gy.device, dtype) if ga is None else ga
+        sx, sa = _pstrides(gx), _pstrides(ga)
+        if sx is None or sa is None or gx.dtype != dtype or ga.dtype != dtype:
+            raise ValueError("compress_backward_data: outputs must be pixel-major in one feature dtype, "
+                             "16-byte aligned")
+        PATH_COUNTS["dgrad_cl_" + _KEYS[dtype]] += 1
+        with torch.cuda.device(gy.device):
+            img = packed_weight(weight, "bwd", dtype)
+            _lib.check(lib.mrp_compress_bwd_data_cl(HALF_DTYPES[dtype], _ptr(gy), gn, gp, n, C, H * W, _ptr(img),
+                                                    _ptr(gx), sx[0], sx[1], _ptr(ga), sa[0], sa[1],
+                                                    _stream(gy.device)), "mrp_compress_bwd_data_cl")
+        return gx, ga
     gy, gs = _node_major(gy)
     gx = torch.empty((n, C, H, W), device=gy.device, dtype=dtype) if gx is None else gx
     ga = torch.empty((n, C, H, W), device=gy.device, dtype=dtype) if ga is None else ga
@@ -265,7 +373,8 @@ def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Ten
 
 
 def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor, want_bias: bool = True,
-                             weight: torch.Tensor = None, bias: torch.Tensor = None, want_weight: bool = True):
+                             weight: torch.Tensor = None, bias: torch.Tensor = None, want_weight: bool = True,
+                             pixel_major: bool = None):
     """(dW (C, 2C, 1, 1), db (C) or None) = (sum_n gy[n] [x[n]; a[n]]^T, sum gy)
     (``mrp_compress_bwd_weight``); None when the kernel declines the shape (H W % 32 != 0).  Given
     the parameters, the results are written straight into a gradient all-reducer's buckets when
@@ -280,9 +389,16 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
         gy = gy.to(dtype)
     if a.dtype != dtype:
         a = a.to(dtype)
-    gy, gs = _node_major(gy)
-    x, xs = _node_major(x)
-    a, as_ = _node_major(a)
+    if pixel_major is None:
+        pixel_major = _cl_route(x)
+    if pixel_major:  # 16-bit pixel-major x: mrp_compress_bwd_weight_cl, gy / a converted once if they differ
+        (gy, gs, gp), (x, xs, xp), (a, as_, ap) = _pixel_major(gy), _pixel_major(x), _pixel_major(a)
+        head = (_ptr(gy), gs, gp, _ptr(x), xs, xp, _ptr(a), as_, ap)
+    else:
+        gy, gs = _node_major(gy)
+        x, xs = _node_major(x)
+        a, as_ = _node_major(a)
+        head = (_ptr(gy), gs, _ptr(x), xs, _ptr(a), as_)
     claimed = []
     dw = grad_out_like(weight) if want_weight and weight is not None and weight.dim() == 4 else None
     if dw is not None:
@@ -298,7 +414,13 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
             db = torch.empty((C,), device=gy.device, dtype=torch.float32)
     P = H * W
     split = _split("wgrad") and C % 64 == 0 and P % 32 == 0
-    if dtype in HALF_DTYPES:
+    key = "wgrad_" + _KEYS[dtype]
+    if pixel_major:
+        nbytes = int(lib.mrp_compress_bwd_weight_cl_workspace(n, C, P))
+        typed_cl = lib.mrp_compress_bwd_weight_cl
+        fn, name = (lambda *args: typed_cl(HALF_DTYPES[dtype], *args)), "mrp_compress_bwd_weight_cl"
+        key = "wgrad_cl_" + _KEYS[dtype]
+    elif dtype in HALF_DTYPES:
         nbytes = int(lib.mrp_compress_bwd_weight_t_workspace(n, C, P))
         typed = lib.mrp_compress_bwd_weight_t
         fn, name = (lambda *args: typed(HALF_DTYPES[dtype], *args)), "mrp_compress_bwd_weight_t"
@@ -312,12 +434,11 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
     try:  # claimed bucket slots go back unless the kernel wrote them (declined shape, error, exception)
         ws = torch.empty((nbytes + 3) // 4, device=gy.device, dtype=torch.float32) if nbytes > 0 else None
         with torch.cuda.device(gy.device):
-            code = fn(_ptr(gy), gs, _ptr(x), xs, _ptr(a), as_, n, C, P, _ptr(dw), _ptr(db), _ptr(ws), nbytes,
-                      _stream(gy.device))
-        if code == _lib.HIP_ERROR_NOT_SUPPORTED:
+            code = fn(*head, n, C, P, _ptr(dw), _ptr(db), _ptr(ws), nbytes, _stream(gy.device))
+        if code == _lib.HIP_ERROR_NOT_SUPPORTED and not pixel_major:
             return None
         _lib.check(code, name)
-        PATH_COUNTS["wgrad_" + _KEYS[dtype]] += 1
+        PATH_COUNTS[key] += 1
         done = True
         return dw, db
     finally:
@@ -401,35 +522,49 @@ def _unpad_planes(t: torch.Tensor, C: int, H: int, W: int) -> torch.Tensor:
     return t.view(n, Cp, Pp)[:, :C, : H * W].contiguous().view(n, C, H, W)
 
 
-def _fwd(weight, bias, x, a):
+def _fwd(weight, bias, x, a, cl=None):
+    """``cl``: the route an autograd function decided once (``_cl_route(x)``), else decided here."""
     n, C, H, W = x.shape
+    if _cl_route(x) if cl is None else cl:
+        return compress_forward(weight, bias, x, a, pixel_major=True)
+    _count_convert(x)
     if kernels_supported(C, H * W, x.dtype):
-        return compress_forward(weight, bias, x, a)
+        return compress_forward(weight, bias, x, a, pixel_major=False)
     Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(x.dtype))
     wp, bp = _padded_params(weight, bias)
-    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a.to(x.dtype), Cp, Pp))
+    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a.to(x.dtype), Cp, Pp), pixel_major=False)
     return _unpad_planes(y, C, H, W)
 
 
-def _bwd_data(weight, gy, dtype=None):
+def _bwd_data(weight, gy, dtype=None, like=None, cl=None):
+    """``like``: the forward's first feature operand — its layout decided the forward's route; ``cl``:
+    that decision as the forward remembered it (an autograd function's ``ctx.cl``)."""
     n, C, H, W = gy.shape
     dtype = gy.dtype if dtype is None else dtype
+    if (like is not None and _cl_route(like)) if cl is None else cl:
+        return compress_backward_data(weight, gy, dtype=dtype, pixel_major=True)
+    if like is not None:
+        _count_convert(like)
     if kernels_supported(C, H * W, dtype):
-        return compress_backward_data(weight, gy, dtype=dtype)
+        return compress_backward_data(weight, gy, dtype=dtype, pixel_major=False)
     Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(dtype))
     wp, _ = _padded_params(weight, None)
-    gx, ga = compress_backward_data(wp, _pad_planes(gy.to(dtype), Cp, Pp))
+    gx, ga = compress_backward_data(wp, _pad_planes(gy.to(dtype), Cp, Pp), pixel_major=False)
     return _unpad_planes(gx, C, H, W), _unpad_planes(ga, C, H, W)
 
 
-def _bwd_weight(gy, x, a, want_bias, weight, bias, want_weight=True):
+def _bwd_weight(gy, x, a, want_bias, weight, bias, want_weight=True, cl=None):
     n, C, H, W = gy.shape
+    if _cl_route(x) if cl is None else cl:
+        return compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight, pixel_major=True)
+    _count_convert(x)
     if kernels_supported(C, H * W, x.dtype):
-        r = compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight)
+        r = compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight, pixel_major=False)
         if r is not None:
             return r
     Cp, Pp = _round(C, 32), _round(H * W, 32)
-    r = compress_backward_weight(*(_pad_planes(t.to(x.dtype), Cp, Pp) for t in (gy, x, a)), want_bias)
+    r = compress_backward_weight(*(_pad_planes(t.to(x.dtype), Cp, Pp) for t in (gy, x, a)), want_bias,
+                                 pixel_major=False)
     if r is None:
         raise RuntimeError(f"mrp_gnn: the compress weight-gradient kernels declined the padded shape C={Cp}, HW={Pp}")
     dwp, dbp = r
@@ -443,9 +578,10 @@ class CompressFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, weight, bias):
         hip = _PATH[0] != "library"
-        y = _fwd(weight, bias, x, a) if hip else _lib_forward(weight, bias, x, a)
+        cl = hip and _cl_route(x)  # decided once: the backward follows the forward's route
+        y = _fwd(weight, bias, x, a, cl=cl) if hip else _lib_forward(weight, bias, x, a)
         ctx.save_for_backward(x, a, weight)
-        ctx.hip, ctx.has_bias = hip, bias is not None
+        ctx.hip, ctx.has_bias, ctx.cl = hip, bias is not None, cl
         return y
 
     @staticmethod
@@ -453,9 +589,9 @@ class CompressFunction(torch.autograd.Function):
         x, a, weight = ctx.saved_tensors
         gx = ga = dw = db = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gx, ga = _bwd_data(weight, gy, x.dtype) if ctx.hip else _lib_backward_data(weight, gy)
+            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl) if ctx.hip else _lib_backward_data(weight, gy)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            dw, db = _bwd_weight(gy, x, a, ctx.has_bias, None, None) if ctx.hip else \
+            dw, db = _bwd_weight(gy, x, a, ctx.has_bias, None, None, cl=ctx.cl) if ctx.hip else \
                 _lib_backward_weight(gy, x, a, ctx.has_bias)
         return gx, ga, dw, db
 
@@ -522,12 +658,15 @@ class FilmCompressFunction(torch.autograd.Function):
     def forward(ctx, x, gb, weight, bias, csr, mode: int):
         from .aggregate import film_mean_forward_into
         n, C, H, W = x.shape
-        agg = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-        film_mean_forward_into(x, gb, csr, mode, agg)
         hip = _PATH[0] != "library"
-        y = _fwd(weight, bias, x, agg) if hip else _lib_forward(weight, bias, x, agg)
+        # a pixel-major 16-bit x: the pixel-major aggregation into a channels_last aggregate, read in place
+        # by the pixel-major compress (no layout copy of x, the aggregate or y)
+        cl = hip and _cl_route(x)  # decided once: the backward follows the forward's route
+        agg = _empty_cl(x.shape, x.device, x.dtype) if cl else torch.empty(x.shape, device=x.device, dtype=x.dtype)
+        film_mean_forward_into(x, gb, csr, mode, agg)
+        y = _fwd(weight, bias, x, agg, cl=cl) if hip else _lib_forward(weight, bias, x, agg)
         ctx.save_for_backward(x, gb, agg, weight, bias)
-        ctx.csr, ctx.mode, ctx.has_bias, ctx.hip = csr, mode, bias is not None, hip
+        ctx.csr, ctx.mode, ctx.has_bias, ctx.hip, ctx.cl = csr, mode, bias is not None, hip, cl
         return y
 
     @staticmethod
@@ -537,15 +676,16 @@ class FilmCompressFunction(torch.autograd.Function):
         need_x, need_gb = ctx.needs_input_grad[0], gb is not None and ctx.needs_input_grad[1]
         dx = dgb = dw = db = None
         if need_x or need_gb:
-            gx, ga = _bwd_data(weight, gy, x.dtype) if ctx.hip else _lib_backward_data(weight, gy)
+            # ctx.cl: channels_last gx / ga straight into the pixel-major aggregation backward
+            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl) if ctx.hip else _lib_backward_data(weight, gy)
             dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                          grad_x_base=gx if need_x else None,
-                                         pixel_major=False)  # the forward above ran the NCHW kernels
+                                         pixel_major=ctx.cl)  # else the forward above ran the NCHW kernels
             if dgb is not None:
                 dgb = dgb.view(gb.shape).to(gb.dtype)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             dw, db = _bwd_weight(gy, x, agg, ctx.has_bias and ctx.needs_input_grad[3], weight, bias,
-                                 want_weight=ctx.needs_input_grad[2]) if ctx.hip else \
+                                 want_weight=ctx.needs_input_grad[2], cl=ctx.cl) if ctx.hip else \
                 _lib_backward_weight(gy, x, agg, ctx.has_bias)
             if not ctx.needs_input_grad[2]:
                 dw = None

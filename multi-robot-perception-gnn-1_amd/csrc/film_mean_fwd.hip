@@ -68,6 +68,8 @@ int mrp_tuning_set(const char* name, int32_t value) {
       {"enc_s2", &t.enc_s2, 0, 64},
       {"compress_half", &t.compress_half, 0, 1},
       {"half_nt_splits", &t.half_nt_splits, 0, 256},
+      {"compress_half_cl", &t.compress_half_cl, 0, 1},
+      {"half_cl_splits", &t.half_cl_splits, 0, 256},
   };
   for (const Knob& k : knobs) {
     if (std::strcmp(name, k.name) == 0) {

@@ -61,6 +61,9 @@ struct Tuning {
   // the weight gradient's split-K count (0: compress_split.hip's planner)
   int compress_half = 1;
   int half_nt_splits = 0;
+  // the pixel-major bf16 / fp16 compress (compress_half_cl.hip): the same two knobs for its entry points
+  int compress_half_cl = 1;
+  int half_cl_splits = 0;
 };
 Tuning& tuning();
 

@@ -172,7 +172,10 @@ class GCN(_PackedImages, nn.Module):
         same route on the 16-bit kernels (``compress_half.hip``) and return their dtype: the weight
         rounded once to it, fp32 accumulation and bias, one rounding at the store, fp32 ``dW`` / ``db``.
         A conv stored in 16 bits, or ``compress.set_half_compress('torch')``: the 16-bit cat kernel,
-        then ``conv(h)`` by torch."""
+        then ``conv(h)`` by torch.  ``torch.channels_last`` bf16 / fp16 features (C % 32 == 0) stay
+        channels_last through the layer and its backward: the pixel-major aggregation and compress
+        kernels read and write them in place (``compress_half_cl.hip``;
+        ``compress.set_channels_last_compress('convert')`` restores the copy to NCHW)."""
         x = feats
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):

@@ -2,8 +2,9 @@
 """Kernel lab (not product code): the 16-bit compress forward and data gradient of the product library
 (A) against a variant library (B, tools/build_variant_lib.py) in one process, the two taking turns call
 by call (tools/bench_half_io.py's method: hipEvents, 5 warm-ups, median of ``iters``, operand sets rotated
-over > 512 MB), at the configs[1] / [2] / [4] layer shapes; outputs compared bit for bit.
-usage: python tools/ab_half_nn.py tools/bin/<variant>.so [iters]"""
+over > 512 MB), at the configs[1] / [2] / [4] layer shapes; outputs compared bit for bit.  With ``cl`` the
+operands are channels_last, so the two libraries' pixel-major kernels (compress_half_cl.hip) are timed.
+usage: python tools/ab_half_nn.py tools/bin/<variant>.so [iters] [cl]"""
 import ctypes
 import os
 import sys
@@ -19,6 +20,7 @@ lib_a = _lib.load_library()
 lib_b = ctypes.CDLL(os.path.abspath(sys.argv[1]))
 _lib._declare(lib_b)
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+layout = torch.channels_last if len(sys.argv) > 3 and sys.argv[3] == "cl" else torch.contiguous_format
 dev = torch.device("cuda:0")
 stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 block_a = torch.empty(256 << 20, device=dev, dtype=torch.uint8)
@@ -44,7 +46,8 @@ with torch.no_grad():
         b = torch.randn(C, device=dev, generator=gen)
         for label, T in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
             k = max(2, -(-MIN_FOOTPRINT // (3 * Nt * C * H * H * 2)) + 1)
-            sets = [tuple(torch.randn(Nt, C, H, H, device=dev, generator=gen).to(T) for _ in range(3)) for _ in range(k)]
+            sets = [tuple(torch.randn(Nt, C, H, H, device=dev, generator=gen).to(T).contiguous(memory_format=layout)
+                          for _ in range(3)) for _ in range(k)]
             fwd = [(lambda x=x, a=a: compress.compress_forward(w, b, x, a)) for x, a, _ in sets]
             dgr = [(lambda gy=gy: compress.compress_backward_data(w, gy)) for _, _, gy in sets]
             res = {}

@@ -353,7 +353,13 @@ int64_t mrp_film_mean_bwd_cl_workspace(int32_t num_graphs, int32_t max_nodes, in
  * conv weight (C, 2C) row-major (nn.Conv2d's (C, 2C, 1, 1)); x and a are the two halves of the
  * concatenation as separate node-major tensors (any node strides, e.g. the two halves of one cat
  * buffer).  Requirements (else hipErrorNotSupported): C % 32 == 0, P % 4 == 0, node strides % 4 == 0,
- * every tensor 16-byte aligned, each operand's node range addressable with 31-bit byte offsets.
+ * every tensor 16-byte aligned, and the node range one workgroup reads addressable with 31-bit byte
+ * offsets: for the forward and the data gradient (128 / P + 2) node strides of x / agg / gy plus one node's
+ * K rows below 2^31 bytes (the offsets are relative to the column tile's first node, not to the tensor, and
+ * the outputs are written through 64-bit addresses: the tensors themselves may span any number of GiB,
+ * tests/test_gpu_large_span.py); the weight gradient splits K so that every split's node range fits
+ * (at most 2^31 / (4 max node stride) - 2 nodes per split and at most 256 splits: a node stride that
+ * leaves less than one node per split, or more nodes than 256 such splits hold, is declined).
  *
  * mrp_compress_fwd:       y[n] = W[:, :C] x[n] + W[:, C:] a[n] + bias      (bias (C) may be NULL)
  * mrp_compress_bwd_data:  gx[n] = W[:, :C]^T gy[n],  ga[n] = W[:, C:]^T gy[n]
@@ -391,6 +397,8 @@ int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, const float
  *   mrp_compress_bwd_data_split           [gx; gagg] = W^T gy with packed = pack(w, 2C, 1, 2C, C)
  * Arguments otherwise as mrp_compress_fwd / mrp_compress_bwd_data.  Requirements (else
  * hipErrorNotSupported): C % 32 == 0, P % 4 == 0, x / agg / gy 16-byte aligned with node strides % 4 == 0.
+ * No span limit: operands and outputs are addressed with 64-bit node offsets (where an output's node range
+ * passes 31-bit byte offsets the 128-row form, whose stores are 64-bit, runs instead of the 256-row one).
  */
 int64_t mrp_compress_split_pack_bytes(int32_t M, int32_t K);
 int mrp_compress_split_pack(const float* w, int64_t ld, int32_t transpose, int32_t M, int32_t K, void* packed,
@@ -438,8 +446,12 @@ int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_stride, const
  * or a workspace that is too small return hipErrorInvalidValue; zero sizes return success without a
  * launch (an empty weight-gradient sum zeroes gw / gbias).  Shapes the kernels do not tile return
  * hipErrorNotSupported: C % 32 != 0, P % 8 != 0 (forward, data gradient), P % 32 != 0 (weight
- * gradient), an operand or output node range beyond 31-bit byte offsets — and every shape while the
- * tuning knob "compress_half" is 0.  No host synchronisation; stream-capturable.
+ * gradient), an output node range beyond 31-bit byte offsets (forward, data gradient: y, gx or gagg with
+ * ((num_nodes - 1) node strides + C P) elements of 2 bytes reaching 2^31 bytes — their stores go through
+ * 32-bit buffer offsets; nodes are independent, so a caller covers a wider output with one call per node
+ * range that fits, as compress.py does; the operands x, agg, gy of all three entry points are read through
+ * 64-bit addresses and may span any number of GiB, and the weight gradient has no span limit) — and every
+ * shape while the tuning knob "compress_half" is 0.  No host synchronisation; stream-capturable.
  */
 int64_t mrp_compress_pack_t_bytes(int32_t M, int32_t K);
 int mrp_compress_pack_t(int32_t dtype, const float* w, int64_t ld, int32_t transpose, int32_t M, int32_t K,

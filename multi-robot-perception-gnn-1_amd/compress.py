@@ -48,6 +48,7 @@ it (``PATH_COUNTS["convert_cl"]`` counts the 16-bit calls that did).
 from __future__ import annotations
 
 import collections
+import ctypes
 import weakref
 
 import torch
@@ -242,6 +243,21 @@ def _node_major(t: torch.Tensor):
     return t, s
 
 
+def _span_nodes(n: int, C: int, P: int, *out_strides: int) -> int:
+    """Nodes per call of ``mrp_compress_fwd_t`` / ``_bwd_data_t``: their stores go through 32-bit buffer
+    offsets, so the entry points decline an output whose node range — (nodes - 1) node strides + C P
+    elements of 2 bytes — reaches 2^31 bytes (``include/mrp_gnn.h``).  Nodes are independent in both products,
+    so a wider output (a sparse view, a batch slice of a far larger buffer) is written by consecutive node
+    ranges that each fit, with the same values."""
+    room = (1 << 30) - 1 - C * P  # elements left for the (nodes - 1) strides
+    return max(1, min(n, 1 + max(room, 0) // max(1, *out_strides)))
+
+
+def _at(t: torch.Tensor, elements: int):
+    """Pointer ``elements`` elements behind t's first."""
+    return ctypes.c_void_p(t.data_ptr() + elements * t.element_size())
+
+
 def _weight2d(weight: torch.Tensor) -> torch.Tensor:
     C = weight.shape[0]
     w = weight.detach().reshape(C, weight.shape[1])
@@ -302,8 +318,11 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
     with torch.cuda.device(x.device):
         if dtype in HALF_DTYPES:
             img = packed_weight(weight, "fwd", dtype)
-            _lib.check(lib.mrp_compress_fwd_t(HALF_DTYPES[dtype], _ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img),
-                                              _ptr(b), _ptr(y), C * H * W, _stream(x.device)), "mrp_compress_fwd_t")
+            k = _span_nodes(n, C, H * W, C * H * W)
+            for i in range(0, n, k):  # one call unless y's node range passes the kernel's 31-bit store offsets
+                _lib.check(lib.mrp_compress_fwd_t(HALF_DTYPES[dtype], _at(x, i * xs), xs, _at(a, i * as_), as_,
+                                                  min(k, n - i), C, H * W, _ptr(img), _ptr(b), _at(y, i * C * H * W),
+                                                  C * H * W, _stream(x.device)), "mrp_compress_fwd_t")
         elif _split("fwd"):
             img = packed_weight(weight, "fwd")
             _lib.check(lib.mrp_compress_fwd_split(_ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img), _ptr(b), _ptr(y),
@@ -356,8 +375,11 @@ def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Ten
     with torch.cuda.device(gy.device):
         if dtype in HALF_DTYPES:
             img = packed_weight(weight, "bwd", dtype)
-            _lib.check(lib.mrp_compress_bwd_data_t(HALF_DTYPES[dtype], _ptr(gy), gs, n, C, H * W, _ptr(img), _ptr(gx),
-                                                   gxs, _ptr(ga), gas, st), "mrp_compress_bwd_data_t")
+            k = _span_nodes(n, C, H * W, gxs, gas)
+            for i in range(0, n, k):  # one call unless an output's node range passes the 31-bit store offsets
+                _lib.check(lib.mrp_compress_bwd_data_t(HALF_DTYPES[dtype], _at(gy, i * gs), gs, min(k, n - i), C, H * W,
+                                                       _ptr(img), _at(gx, i * gxs), gxs, _at(ga, i * gas), gas, st),
+                           "mrp_compress_bwd_data_t")
             return gx, ga
         if _split("dgrad"):
             img = packed_weight(weight, "bwd")

@@ -423,6 +423,47 @@ int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_stride, const
                                   float* gw, float* gbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * The three split-bf16 compress products with a selectable part count: the arguments of
+ * mrp_compress_fwd_split / _bwd_data_split / _bwd_weight_split plus `parts` before `stream`.  A kernel
+ * with `parts` = 3 / 2 / 1 keeps the first `parts` bf16 parts of each fp32 operand (x = x0 + x1 + x2, each
+ * part the bf16 rounding of what the earlier ones left) and sums the partial products a_i b_j with
+ * i + j < parts: six, three (a0 b0 + a0 b1 + a1 b0, "bf16x3") or one (bf16 operands).  The dropped
+ * parts are not converted, not staged in LDS, not read and — for the packed weight image, whose parts
+ * are separate 1 KiB pieces — not fetched; the image itself is mrp_compress_split_pack's three-part one
+ * for every `parts` (no repack when the count changes).  a0 b0 accumulates alone, the other products in
+ * a second fp32 accumulator, the two summed once at the end.
+ * Error model, per term a_k b_k of a product (then fp32 accumulation of the partial sums as above):
+ *   parts = 3: the omitted terms are below 2^-25 |a_k b_k| (the existing entry points' model);
+ *   parts = 2: the dropped terms are a1 b1 and the two-part residuals (a - a0 - a1) b, a (b - b0 - b1):
+ *              with a rounding unit of 2^-9 per bf16 part (|a1| <= 2^-9 |a|, residual <= 2^-18 |a|)
+ *              at most (2^-18 + 2 x 2^-18 + higher orders) |a_k b_k| <= 3.1 x 2^-18 |a_k b_k|;
+ *   parts = 1: |a - a0| <= 2^-9 |a| in both operands: at most 2.01 x 2^-9 |a_k b_k|.
+ *   These are the bounds tests/test_gpu_compress_precision.py holds the kernels to against
+ *   sum_k |a_k b_k|.  2^-9 is the rounding unit of a value just below a power of two; just above one a
+ *   bf16 step is twice as wide (bf16 carries 8 significant bits: unit 2^-8), so a single term can reach
+ *   2.01 x 2^-8 (parts = 1) and 3.1 x 2^-16 (parts = 2) of itself.  Over a sum the roundings do not
+ *   align: measured errors are recorded in DESIGN.md §3.11.
+ * gbias is the fp32 sum of the full gy for every `parts`, never of a truncated image.
+ * Returns: `parts` outside {1, 2, 3}: hipErrorInvalidValue before anything else; zero sizes: success
+ * without a launch (the weight gradient's empty sum zeroes its outputs as _bwd_weight_split does);
+ * hipErrorNotSupported exactly where the existing entry point returns it; parts = 3 is the existing
+ * entry point (bit-identical — the existing ones call these with 3).
+ * mrp_compress_bwd_weight_split_workspace(num_nodes, C, P) is the workspace bound for every `parts`: a
+ * reduced form never needs more (its pre-split image of gy takes 2 parts bytes per element of the six
+ * the bound reserves, at the same offsets).
+ */
+int mrp_compress_fwd_split_p(const float* x, int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
+                             int32_t num_nodes, int32_t C, int32_t P, const void* packed_w, const float* bias,
+                             float* y, int64_t y_node_stride, int32_t parts, void* stream);
+int mrp_compress_bwd_data_split_p(const float* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C, int32_t P,
+                                  const void* packed_wt, float* gx, int64_t gx_node_stride, float* gagg,
+                                  int64_t gagg_node_stride, int32_t parts, void* stream);
+int mrp_compress_bwd_weight_split_p(const float* gy, int64_t gy_node_stride, const float* x, int64_t x_node_stride,
+                                    const float* a, int64_t a_node_stride, int32_t num_nodes, int32_t C, int32_t P,
+                                    float* gw, float* gbias, void* workspace, int64_t workspace_bytes,
+                                    int32_t parts, void* stream);
+
+/*
  * The compress forward and both gradients on bf16 / fp16 feature maps (compress_half.hip; dtype is
  * MRP_DTYPE_BF16 or MRP_DTYPE_F16 = T, the storage type of x, agg, y, gy, gx and gagg; the parameters
  * and their gradients are fp32).  The same products as the _split entry points, one
@@ -686,7 +727,8 @@ int mrp_tuning_set(const char* name, int32_t value);
  * typed compress entry points mrp_compress_pack_t_bytes / _pack_t / _fwd_t / _bwd_data_t /
  * _bwd_weight_t_workspace / _bwd_weight_t and the knobs "compress_half" / "half_nt_splits", and their
  * pixel-major forms mrp_compress_fwd_cl / _bwd_data_cl / _bwd_weight_cl_workspace / _bwd_weight_cl with the
- * knobs "compress_half_cl" / "half_cl_splits"; 21: v19 plus
+ * knobs "compress_half_cl" / "half_cl_splits", and the part-count forms of the split-bf16 compress
+ * mrp_compress_fwd_split_p / _bwd_data_split_p / _bwd_weight_split_p; 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

@@ -41,6 +41,9 @@ EXPORTED_SYMBOLS = (
     "mrp_compress_bwd_data_split",
     "mrp_compress_bwd_weight_split_workspace",
     "mrp_compress_bwd_weight_split",
+    "mrp_compress_fwd_split_p",
+    "mrp_compress_bwd_data_split_p",
+    "mrp_compress_bwd_weight_split_p",
     "mrp_compress_pack_t_bytes",
     "mrp_compress_pack_t",
     "mrp_compress_fwd_t",
@@ -173,6 +176,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_compress_bwd_weight_split_workspace.restype = ctypes.c_int64
     lib.mrp_compress_bwd_weight_split.argtypes = lib.mrp_compress_bwd_weight.argtypes
     lib.mrp_compress_bwd_weight_split.restype = ctypes.c_int
+    # the same with a trailing part count (3 / 2 / 1 bf16 parts kept per operand) before the stream
+    lib.mrp_compress_fwd_split_p.argtypes = lib.mrp_compress_fwd_split.argtypes[:-1] + [_I32, _P]
+    lib.mrp_compress_fwd_split_p.restype = ctypes.c_int
+    lib.mrp_compress_bwd_data_split_p.argtypes = lib.mrp_compress_bwd_data_split.argtypes[:-1] + [_I32, _P]
+    lib.mrp_compress_bwd_data_split_p.restype = ctypes.c_int
+    lib.mrp_compress_bwd_weight_split_p.argtypes = lib.mrp_compress_bwd_weight.argtypes[:-1] + [_I32, _P]
+    lib.mrp_compress_bwd_weight_split_p.restype = ctypes.c_int
     lib.mrp_compress_pack_t_bytes.argtypes = [_I32, _I32]
     lib.mrp_compress_pack_t_bytes.restype = ctypes.c_int64
     lib.mrp_compress_pack_t.argtypes = [_I32] + lib.mrp_compress_split_pack.argtypes

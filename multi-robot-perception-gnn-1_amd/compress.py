@@ -37,6 +37,14 @@ Their tiles need C % 32 == 0 and H W % 8 == 0 (32 for the weight gradient); othe
 zero-padded as above.  :func:`set_half_compress` ``("torch")`` restores the earlier route (the 16-bit
 cat kernel + torch's convolution) for A/B runs; :data:`PATH_COUNTS` counts the launches per route.
 
+Precision of the ``"split"`` path on fp32 features (:func:`set_compress_precision`): ``"highest"``
+(default) keeps all three bf16 parts of every operand and the six partial products; ``"high"`` keeps two
+parts and the three products ``a0 b0 + a0 b1 + a1 b0`` (per-term error at most 3.1 x 2^-18, about 100 x
+finer than TF32); ``"medium"`` keeps one part and one product (bf16 operands, fp32 accumulation and
+output; per-term error at most 2.01 x 2^-9).  The reduced forms skip the dropped parts' conversions, LDS
+traffic and MFMAs (``mrp_compress_fwd_split_p`` / ``_bwd_data_split_p`` / ``_bwd_weight_split_p``); the
+packed weight images and ``db`` (the fp32 sum of the full ``dy``) are the same in every mode.
+
 Pixel-major (``torch.channels_last``) bf16 / fp16 feature maps with C % 32 == 0 run the three products
 on kernels of their own (``csrc/compress_half_cl.hip``: ``mrp_compress_fwd_cl`` / ``_bwd_data_cl`` /
 ``_bwd_weight_cl``), which read the features in place — dense maps or the halves of a channels_last
@@ -48,6 +56,7 @@ it (``PATH_COUNTS["convert_cl"]`` counts the 16-bit calls that did).
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import weakref
 
@@ -68,7 +77,55 @@ _KEYS = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
 #: Which route ran: ``fwd_*`` / ``dgrad_*`` / ``wgrad_*`` for each of ``f32`` / ``bf16`` / ``f16`` count
 #: the kernel launches of this module per feature dtype; ``torch_16`` counts 16-bit layers handed to
 #: torch's convolution (:func:`compress_1x1` with ``set_half_compress("torch")``, or a conv stored in T).
+#: fp32 calls that ran a reduced split form count under ``fwd_f32_high`` / ``dgrad_f32_high`` /
+#: ``wgrad_f32_high`` (and ``_medium``) instead of the plain ``_f32`` keys.
 PATH_COUNTS = collections.Counter()
+
+#: precision mode -> bf16 parts kept per operand (the products kept are those with i + j < parts)
+PRECISION_PARTS = {"highest": 3, "high": 2, "medium": 1}
+_PRECISION = ["highest"]
+
+
+def set_compress_precision(mode: str) -> str:
+    """Precision of the fp32 products on the ``"split"`` compress path: ``"highest"`` (default) six partial
+    products per product, fp32 accuracy; ``"high"`` two bf16 parts per operand and three products (bf16x3,
+    per-term error <= 3.1 x 2^-18); ``"medium"`` one part and one product (bf16 operands, fp32 accumulation,
+    per-term error <= 2.01 x 2^-9).  Applies to fp32 features only — zero-padded odd shapes, per-node-range
+    calls and the convert route of fp32 channels_last features included, which all end in the same kernels.
+    ``set_compress_path("hip" | "library")`` and bf16 / fp16 features ignore the mode.  An autograd node
+    keeps the mode its forward ran in for both of its gradients.  Returns the previous mode."""
+    if mode not in PRECISION_PARTS:
+        raise ValueError("compress precision must be 'highest', 'high' or 'medium'")
+    prev, _PRECISION[0] = _PRECISION[0], mode
+    return prev
+
+
+def compress_precision() -> str:
+    """The current mode of :func:`set_compress_precision`."""
+    return _PRECISION[0]
+
+
+@contextlib.contextmanager
+def compress_precision_scope(mode: str):
+    """``with compress_precision_scope("high"): ...`` — the mode inside, the previous one restored on the way
+    out (also when the body raises).  Split-path fp32 products only; see :func:`set_compress_precision`."""
+    prev = set_compress_precision(mode)
+    try:
+        yield
+    finally:
+        _PRECISION[0] = prev
+
+
+def _mode(precision) -> str:
+    if precision is None:
+        return _PRECISION[0]
+    if precision not in PRECISION_PARTS:
+        raise ValueError("compress precision must be 'highest', 'high' or 'medium'")
+    return precision
+
+
+def _mode_key(key: str, mode: str) -> str:
+    return key if mode == "highest" else key + "_" + mode
 
 _HALF = ["native"]
 
@@ -283,9 +340,11 @@ def kernels_supported(C: int, P: int, dtype: torch.dtype = torch.float32) -> boo
 
 
 def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tensor,
-                     pixel_major: bool = None) -> torch.Tensor:
+                     pixel_major: bool = None, precision: str = None) -> torch.Tensor:
     """``conv(torch.cat((x, a), 1))`` for a (C, 2C, 1, 1) weight without the concatenation
-    (``mrp_compress_fwd``); x and a are (N, C, H, W), e.g. views of a cat buffer's halves."""
+    (``mrp_compress_fwd``); x and a are (N, C, H, W), e.g. views of a cat buffer's halves.  ``precision``:
+    the mode of the fp32 split product (default: :func:`compress_precision`); ignored by bf16 / fp16
+    features and by the ``"hip"`` path."""
     from .aggregate import _ptr, _stream
     n, C, H, W = x.shape
     dtype = x.dtype  # the feature dtype: a is cast to it, y is allocated in it
@@ -314,7 +373,8 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
         b = b.float().contiguous()
     y = torch.empty((n, C, H, W), device=x.device, dtype=dtype)
     lib = _lib.load_library()
-    PATH_COUNTS["fwd_" + _KEYS[dtype]] += 1
+    mode = _mode(precision) if dtype == torch.float32 and _split("fwd") else "highest"
+    PATH_COUNTS[_mode_key("fwd_" + _KEYS[dtype], mode)] += 1
     with torch.cuda.device(x.device):
         if dtype in HALF_DTYPES:
             img = packed_weight(weight, "fwd", dtype)
@@ -323,6 +383,11 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
                 _lib.check(lib.mrp_compress_fwd_t(HALF_DTYPES[dtype], _at(x, i * xs), xs, _at(a, i * as_), as_,
                                                   min(k, n - i), C, H * W, _ptr(img), _ptr(b), _at(y, i * C * H * W),
                                                   C * H * W, _stream(x.device)), "mrp_compress_fwd_t")
+        elif _split("fwd") and mode != "highest":
+            img = packed_weight(weight, "fwd")  # the same three-part image: a reduced form fetches fewer parts
+            _lib.check(lib.mrp_compress_fwd_split_p(_ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img), _ptr(b), _ptr(y),
+                                                    C * H * W, PRECISION_PARTS[mode], _stream(x.device)),
+                       "mrp_compress_fwd_split_p")
         elif _split("fwd"):
             img = packed_weight(weight, "fwd")
             _lib.check(lib.mrp_compress_fwd_split(_ptr(x), xs, _ptr(a), as_, n, C, H * W, _ptr(img), _ptr(b), _ptr(y),
@@ -334,13 +399,13 @@ def compress_forward(weight: torch.Tensor, bias, x: torch.Tensor, a: torch.Tenso
 
 
 def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor = None, ga: torch.Tensor = None,
-                           dtype: torch.dtype = None, pixel_major: bool = None):
+                           dtype: torch.dtype = None, pixel_major: bool = None, precision: str = None):
     """(gx, ga) = (W[:, :C]^T gy, W[:, C:]^T gy) per node (``mrp_compress_bwd_data``), written into
     the given (N, C, H, W) outputs (e.g. the halves of a cat buffer's gradient) or new tensors.  The
     feature dtype is the given outputs', else ``dtype``, else gy's; gy is cast to it.  16-bit pixel-major
     outputs (or, with none given, a pixel-major gy — or ``pixel_major=True``, the layout of the forward's
     features) take the pixel-major kernel (``mrp_compress_bwd_data_cl``): new outputs are dense
-    channels_last, a gy in the other layout is converted once."""
+    channels_last, a gy in the other layout is converted once.  ``precision``: as :func:`compress_forward`."""
     from .aggregate import _ptr, _stream
     n, C, H, W = gy.shape
     lib = _lib.load_library()
@@ -371,7 +436,8 @@ def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Ten
     if gxs is None or gas is None or gx.dtype != dtype or ga.dtype != dtype:
         raise ValueError("compress_backward_data: outputs must be node-major in one feature dtype, 16-byte aligned")
     st = _stream(gy.device)
-    PATH_COUNTS["dgrad_" + _KEYS[dtype]] += 1
+    mode = _mode(precision) if dtype == torch.float32 and _split("dgrad") else "highest"
+    PATH_COUNTS[_mode_key("dgrad_" + _KEYS[dtype], mode)] += 1
     with torch.cuda.device(gy.device):
         if dtype in HALF_DTYPES:
             img = packed_weight(weight, "bwd", dtype)
@@ -380,6 +446,12 @@ def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Ten
                 _lib.check(lib.mrp_compress_bwd_data_t(HALF_DTYPES[dtype], _at(gy, i * gs), gs, min(k, n - i), C, H * W,
                                                        _ptr(img), _at(gx, i * gxs), gxs, _at(ga, i * gas), gas, st),
                            "mrp_compress_bwd_data_t")
+            return gx, ga
+        if _split("dgrad") and mode != "highest":
+            img = packed_weight(weight, "bwd")
+            _lib.check(lib.mrp_compress_bwd_data_split_p(_ptr(gy), gs, n, C, H * W, _ptr(img), _ptr(gx), gxs, _ptr(ga),
+                                                         gas, PRECISION_PARTS[mode], st),
+                       "mrp_compress_bwd_data_split_p")
             return gx, ga
         if _split("dgrad"):
             img = packed_weight(weight, "bwd")
@@ -396,12 +468,14 @@ def compress_backward_data(weight: torch.Tensor, gy: torch.Tensor, gx: torch.Ten
 
 def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor, want_bias: bool = True,
                              weight: torch.Tensor = None, bias: torch.Tensor = None, want_weight: bool = True,
-                             pixel_major: bool = None):
+                             pixel_major: bool = None, precision: str = None):
     """(dW (C, 2C, 1, 1), db (C) or None) = (sum_n gy[n] [x[n]; a[n]]^T, sum gy)
     (``mrp_compress_bwd_weight``); None when the kernel declines the shape (H W % 32 != 0).  Given
     the parameters, the results are written straight into a gradient all-reducer's buckets when
     one holds them (``dist.grad_out_like``) — only for a gradient that is wanted, and the slots are
-    given back (``dist.release_grad_out``) when the kernel declines the shape."""
+    given back (``dist.release_grad_out``) when the kernel declines the shape.  ``precision``: as
+    :func:`compress_forward` (the split kernels only: where the weight gradient falls back to the fp32 MFMA
+    it is exact fp32 and counts under the plain key); db is the fp32 sum of the full gy in every mode."""
     from .aggregate import _ptr, _stream
     from .dist import grad_out_like, release_grad_out
     n, C, H, W = gy.shape
@@ -446,6 +520,12 @@ def compress_backward_weight(gy: torch.Tensor, x: torch.Tensor, a: torch.Tensor,
         nbytes = int(lib.mrp_compress_bwd_weight_t_workspace(n, C, P))
         typed = lib.mrp_compress_bwd_weight_t
         fn, name = (lambda *args: typed(HALF_DTYPES[dtype], *args)), "mrp_compress_bwd_weight_t"
+    elif split and _mode(precision) != "highest":
+        mode = _mode(precision)
+        nbytes = int(lib.mrp_compress_bwd_weight_split_workspace(n, C, P))  # the bound for every part count
+        split_p = lib.mrp_compress_bwd_weight_split_p
+        fn = lambda *args: split_p(*args[:-1], PRECISION_PARTS[mode], args[-1])  # noqa: E731
+        name, key = "mrp_compress_bwd_weight_split_p", _mode_key(key, mode)
     elif split:
         nbytes = int(lib.mrp_compress_bwd_weight_split_workspace(n, C, P))
         fn, name = lib.mrp_compress_bwd_weight_split, "mrp_compress_bwd_weight_split"
@@ -544,23 +624,26 @@ def _unpad_planes(t: torch.Tensor, C: int, H: int, W: int) -> torch.Tensor:
     return t.view(n, Cp, Pp)[:, :C, : H * W].contiguous().view(n, C, H, W)
 
 
-def _fwd(weight, bias, x, a, cl=None):
-    """``cl``: the route an autograd function decided once (``_cl_route(x)``), else decided here."""
+def _fwd(weight, bias, x, a, cl=None, precision=None):
+    """``cl``: the route an autograd function decided once (``_cl_route(x)``), else decided here;
+    ``precision``: likewise the mode it read once (``ctx.precision``)."""
     n, C, H, W = x.shape
     if _cl_route(x) if cl is None else cl:
         return compress_forward(weight, bias, x, a, pixel_major=True)
     _count_convert(x)
     if kernels_supported(C, H * W, x.dtype):
-        return compress_forward(weight, bias, x, a, pixel_major=False)
+        return compress_forward(weight, bias, x, a, pixel_major=False, precision=precision)
     Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(x.dtype))
     wp, bp = _padded_params(weight, bias)
-    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a.to(x.dtype), Cp, Pp), pixel_major=False)
+    y = compress_forward(wp, bp, _pad_planes(x, Cp, Pp), _pad_planes(a.to(x.dtype), Cp, Pp), pixel_major=False,
+                         precision=precision)
     return _unpad_planes(y, C, H, W)
 
 
-def _bwd_data(weight, gy, dtype=None, like=None, cl=None):
+def _bwd_data(weight, gy, dtype=None, like=None, cl=None, precision=None):
     """``like``: the forward's first feature operand — its layout decided the forward's route; ``cl``:
-    that decision as the forward remembered it (an autograd function's ``ctx.cl``)."""
+    that decision as the forward remembered it (an autograd function's ``ctx.cl``); ``precision``: the
+    forward's mode (``ctx.precision``)."""
     n, C, H, W = gy.shape
     dtype = gy.dtype if dtype is None else dtype
     if (like is not None and _cl_route(like)) if cl is None else cl:
@@ -568,25 +651,26 @@ def _bwd_data(weight, gy, dtype=None, like=None, cl=None):
     if like is not None:
         _count_convert(like)
     if kernels_supported(C, H * W, dtype):
-        return compress_backward_data(weight, gy, dtype=dtype, pixel_major=False)
+        return compress_backward_data(weight, gy, dtype=dtype, pixel_major=False, precision=precision)
     Cp, Pp = _round(C, 32), _round(H * W, _pixel_multiple(dtype))
     wp, _ = _padded_params(weight, None)
-    gx, ga = compress_backward_data(wp, _pad_planes(gy.to(dtype), Cp, Pp), pixel_major=False)
+    gx, ga = compress_backward_data(wp, _pad_planes(gy.to(dtype), Cp, Pp), pixel_major=False, precision=precision)
     return _unpad_planes(gx, C, H, W), _unpad_planes(ga, C, H, W)
 
 
-def _bwd_weight(gy, x, a, want_bias, weight, bias, want_weight=True, cl=None):
+def _bwd_weight(gy, x, a, want_bias, weight, bias, want_weight=True, cl=None, precision=None):
     n, C, H, W = gy.shape
     if _cl_route(x) if cl is None else cl:
         return compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight, pixel_major=True)
     _count_convert(x)
     if kernels_supported(C, H * W, x.dtype):
-        r = compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight, pixel_major=False)
+        r = compress_backward_weight(gy, x, a, want_bias, weight, bias, want_weight=want_weight, pixel_major=False,
+                                     precision=precision)
         if r is not None:
             return r
     Cp, Pp = _round(C, 32), _round(H * W, 32)
     r = compress_backward_weight(*(_pad_planes(t.to(x.dtype), Cp, Pp) for t in (gy, x, a)), want_bias,
-                                 pixel_major=False)
+                                 pixel_major=False, precision=precision)
     if r is None:
         raise RuntimeError(f"mrp_gnn: the compress weight-gradient kernels declined the padded shape C={Cp}, HW={Pp}")
     dwp, dbp = r
@@ -601,9 +685,10 @@ class CompressFunction(torch.autograd.Function):
     def forward(ctx, x, a, weight, bias):
         hip = _PATH[0] != "library"
         cl = hip and _cl_route(x)  # decided once: the backward follows the forward's route
-        y = _fwd(weight, bias, x, a, cl=cl) if hip else _lib_forward(weight, bias, x, a)
+        mode = _PRECISION[0]  # read once: both gradients of this node run in the forward's mode
+        y = _fwd(weight, bias, x, a, cl=cl, precision=mode) if hip else _lib_forward(weight, bias, x, a)
         ctx.save_for_backward(x, a, weight)
-        ctx.hip, ctx.has_bias, ctx.cl = hip, bias is not None, cl
+        ctx.hip, ctx.has_bias, ctx.cl, ctx.precision = hip, bias is not None, cl, mode
         return y
 
     @staticmethod
@@ -611,10 +696,11 @@ class CompressFunction(torch.autograd.Function):
         x, a, weight = ctx.saved_tensors
         gx = ga = dw = db = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl) if ctx.hip else _lib_backward_data(weight, gy)
+            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl, precision=ctx.precision) if ctx.hip else \
+                _lib_backward_data(weight, gy)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            dw, db = _bwd_weight(gy, x, a, ctx.has_bias, None, None, cl=ctx.cl) if ctx.hip else \
-                _lib_backward_weight(gy, x, a, ctx.has_bias)
+            dw, db = _bwd_weight(gy, x, a, ctx.has_bias, None, None, cl=ctx.cl, precision=ctx.precision) if ctx.hip \
+                else _lib_backward_weight(gy, x, a, ctx.has_bias)
         return gx, ga, dw, db
 
 
@@ -686,9 +772,10 @@ class FilmCompressFunction(torch.autograd.Function):
         cl = hip and _cl_route(x)  # decided once: the backward follows the forward's route
         agg = _empty_cl(x.shape, x.device, x.dtype) if cl else torch.empty(x.shape, device=x.device, dtype=x.dtype)
         film_mean_forward_into(x, gb, csr, mode, agg)
-        y = _fwd(weight, bias, x, agg, cl=cl) if hip else _lib_forward(weight, bias, x, agg)
+        prec = _PRECISION[0]  # read once: both gradients of this node run in the forward's mode
+        y = _fwd(weight, bias, x, agg, cl=cl, precision=prec) if hip else _lib_forward(weight, bias, x, agg)
         ctx.save_for_backward(x, gb, agg, weight, bias)
-        ctx.csr, ctx.mode, ctx.has_bias, ctx.hip, ctx.cl = csr, mode, bias is not None, hip, cl
+        ctx.csr, ctx.mode, ctx.has_bias, ctx.hip, ctx.cl, ctx.precision = csr, mode, bias is not None, hip, cl, prec
         return y
 
     @staticmethod
@@ -699,7 +786,8 @@ class FilmCompressFunction(torch.autograd.Function):
         dx = dgb = dw = db = None
         if need_x or need_gb:
             # ctx.cl: channels_last gx / ga straight into the pixel-major aggregation backward
-            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl) if ctx.hip else _lib_backward_data(weight, gy)
+            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=ctx.cl, precision=ctx.precision) if ctx.hip else \
+                _lib_backward_data(weight, gy)
             dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                          grad_x_base=gx if need_x else None,
                                          pixel_major=ctx.cl)  # else the forward above ran the NCHW kernels
@@ -707,7 +795,7 @@ class FilmCompressFunction(torch.autograd.Function):
                 dgb = dgb.view(gb.shape).to(gb.dtype)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             dw, db = _bwd_weight(gy, x, agg, ctx.has_bias and ctx.needs_input_grad[3], weight, bias,
-                                 want_weight=ctx.needs_input_grad[2], cl=ctx.cl) if ctx.hip else \
+                                 want_weight=ctx.needs_input_grad[2], cl=ctx.cl, precision=ctx.precision) if ctx.hip else \
                 _lib_backward_weight(gy, x, agg, ctx.has_bias)
             if not ctx.needs_input_grad[2]:
                 dw = None

@@ -30,6 +30,11 @@
 // where M % 256 == 0 — every reference configuration — else WMW = 2 on 32x32x16 (2 x 2 blocks of
 // 32 x 32).  The weight gradient (below) runs the same structure on two activation operands, and with
 // its dy operand split once (gemm_nt_psa).  Round 4's other forms are lab forms (tools/lab_forms.hip).
+//
+// Part count.  Every kernel of the compress takes a compile-time NP = 3 / 2 / 1: the bf16 parts kept per
+// operand, with the partial products i + j < NP (six, three, one).  The reduced forms skip the dropped
+// parts' conversions, LDS stores, fragment reads, weight-image pieces and MFMAs (mrp_compress_*_split_p;
+// DESIGN.md §3.11); the numbers above are NP = 3's.  The encoder's kernels here stay at NP = 3.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,14 +62,16 @@ typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 constexpr int TN = 128, BK = 32;
 constexpr int B_PART_BYTES = BK * TN * 2;  // one bf16 part of the B stage: 8 KiB
 
-// Workgroup geometry: WMW x 2 waves of 64 x 64, TM = 64 WMW rows.
-template <int WMW>
+// Workgroup geometry: WMW x 2 waves of 64 x 64, TM = 64 WMW rows; NP = the bf16 parts kept per operand
+// (3: six partial products; 2: three; 1: one — DESIGN.md §3.11).  A reduced form stages only its NP
+// parts of either operand: the stage shrinks with NP.
+template <int WMW, int NP = 3>
 struct Geo {
   static constexpr int TM = 64 * WMW, NW = 2 * WMW, THREADS = 64 * NW;
-  static constexpr int A_PIECES = (TM / 32) * (BK / 16) * 3;  // 1 KiB pieces per stage (6 per wave)
+  static constexpr int A_PIECES = (TM / 32) * (BK / 16) * NP;  // 1 KiB pieces per stage (2 NP per wave)
   static constexpr int A_BYTES = A_PIECES * 1024;
-  static constexpr int BUF_BYTES = A_BYTES + 3 * B_PART_BYTES;
-  static constexpr int LDS_BYTES = 2 * BUF_BYTES;  // 96 KiB (WMW 2), 144 KiB (WMW 4)
+  static constexpr int BUF_BYTES = A_BYTES + NP * B_PART_BYTES;
+  static constexpr int LDS_BYTES = 2 * BUF_BYTES;  // NP 3: 96 KiB (WMW 2), 144 KiB (WMW 4); x NP / 3
   static constexpr int BJ = BK * TN / 4 / THREADS;  // 16-byte B pieces per thread per stage
   static constexpr int KR = THREADS / 32;           // B rows per pass
 };
@@ -86,6 +93,20 @@ __device__ __forceinline__ void split2(f2 x, uint32_t& a, uint32_t& b, uint32_t&
   c = cvt2(r2);
 }
 
+// the first NP parts of the same split (NP 3: split2's; the parts a reduced form drops are never computed)
+template <int NP>
+__device__ __forceinline__ void splitp(f2 x, uint32_t (&p)[NP]) {
+  p[0] = cvt2(x);
+  if constexpr (NP > 1) {
+    const f2 r1 = x - widen2(p[0]);
+    p[1] = cvt2(r1);
+    if constexpr (NP > 2) {
+      const f2 r2 = r1 - widen2(p[1]);
+      p[2] = cvt2(r2);
+    }
+  }
+}
+
 // The six partial products of one 16-k step into two accumulators: the five small ones (at most 2^-8
 // of the product) into `lo`, a0 b0 into `hi`, summed once in the epilogue.  The bf16 MFMA rounds its
 // sum into the accumulator to nearest, but where the accumulator is large against the products the
@@ -95,12 +116,19 @@ __device__ __forceinline__ void split2(f2 x, uint32_t& a, uint32_t& b, uint32_t&
 struct Acc2 {
   f16v hi, lo;
 };
-__device__ __forceinline__ void mma6(const bf8 (&a)[3], const bf8 (&b)[3], Acc2& acc) {
-  acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc.lo, 0, 0, 0);
+// With NP parts kept the products are those with i + j < NP: six, three (a0 b1 and a1 b0 into `lo`) or
+// a0 b0 alone (`lo` stays zero).
+template <int NP>
+__device__ __forceinline__ void mma6(const bf8 (&a)[NP], const bf8 (&b)[NP], Acc2& acc) {
+  if constexpr (NP > 2) {
+    acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc.lo, 0, 0, 0);
+  }
+  if constexpr (NP > 1) {
+    acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc.lo, 0, 0, 0);
+  }
   acc.hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc.hi, 0, 0, 0);
 }
 
@@ -109,13 +137,31 @@ typedef float f4acc __attribute__((ext_vector_type(4)));
 struct Acc2s {
   f4acc hi, lo;
 };
-__device__ __forceinline__ void mma6_16(const bf8 (&a)[3], const bf8 (&b)[3], Acc2s& acc) {
-  acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc.lo, 0, 0, 0);
-  acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc.lo, 0, 0, 0);
+template <int NP>
+__device__ __forceinline__ void mma6_16(const bf8 (&a)[NP], const bf8 (&b)[NP], Acc2s& acc) {
+  if constexpr (NP > 2) {
+    acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc.lo, 0, 0, 0);
+  }
+  if constexpr (NP > 1) {
+    acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc.lo, 0, 0, 0);
+    acc.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc.lo, 0, 0, 0);
+  }
   acc.hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc.hi, 0, 0, 0);
+}
+
+// s_waitcnt lgkmcnt(N) with a compile-time count (the counter holds at most 15)
+template <int N>
+__device__ __forceinline__ void wait_lgkm() {
+  static_assert(N >= 0, "lgkmcnt");
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N < 15 ? N : 15) : "memory");
+}
+// keep NP fragment registers behind the wait above them
+template <int NP>
+__device__ __forceinline__ void pin(u4 (&r)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(r[p]));
 }
 
 // byte offset of 16-byte chunk ch (8 columns) of row `row` in a [BK][TN] bf16 image
@@ -187,9 +233,9 @@ __device__ __forceinline__ void tile_of(int t, int mtiles, int ntiles, int group
   nt = rem / gm;
 }
 
-template <int WMW, bool MF16 = false>
+template <int WMW, bool MF16 = false, int NP = 3>
 __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
-  using G = Geo<WMW>;
+  using G = Geo<WMW, NP>;
   constexpr int TM = G::TM, NW = G::NW, A_PIECES = G::A_PIECES, A_BYTES = G::A_BYTES, BUF_BYTES = G::BUF_BYTES;
   extern __shared__ u4 lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
@@ -206,13 +252,15 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
   const int wm = w >> 1, wn = w & 1;
   const int KS = a.K / 16, nst = a.K / BK, ks0 = a.k0 / BK, MB = a.M / 32;
 
-  // ---- A: LDS-DMA pieces pc = (mbl 2 + ksl) 3 + p (local m block, 16-k step, part), pc = w + NW i
+  // ---- A: LDS-DMA pieces pc = (mbl 2 + ksl) NP + p (local m block, 16-k step, part), pc = w + NW i.
+  // The packed image always holds three parts per (block, step) as separate 1 KiB pieces: a reduced
+  // form fetches the first NP of them and packs them densely in LDS.
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.ap);
   uint32_t va[A_PIECES / NW];
 #pragma unroll
   for (int i = 0; i < A_PIECES / NW; ++i) {
     const int pc = w + NW * i;
-    const int mbl = pc / 6, kp = pc % 6;  // kp = 3 ksl + p
+    const int mbl = pc / (2 * NP), kp = 3 * ((pc / NP) & 1) + pc % NP;  // kp = 3 ksl + p
     const int mb = min(mt * (TM / 32) + mbl, MB - 1);  // blocks past M: any valid data, never stored
     va[i] = (uint32_t)((((int64_t)mb * KS * 3 + kp) * 64 + lane) * 16);
   }
@@ -236,21 +284,22 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
 #pragma unroll
     for (int j = 0; j < G::BJ; ++j) breg[j] = *reinterpret_cast<const f4*>(p + (int64_t)G::KR * j * a.P);
   };
-  auto store_b = [&](int buf) {  // split the registers' stage into the buffer's three part images
+  auto store_b = [&](int buf) {  // split the registers' stage into the buffer's NP part images
     char* bimg = ldsb + buf * BUF_BYTES + A_BYTES;
 #pragma unroll
     for (int j = 0; j < G::BJ; ++j) {
-      u2 p0, p1, p2;
       f2 lo, hi;
       lo.x = breg[j].x, lo.y = breg[j].y, hi.x = breg[j].z, hi.y = breg[j].w;
-      uint32_t l0, l1, l2, h0, h1, h2;
-      split2(lo, l0, l1, l2);
-      split2(hi, h0, h1, h2);
-      p0.x = l0, p1.x = l1, p2.x = l2, p0.y = h0, p1.y = h1, p2.y = h2;
+      uint32_t l[NP], h[NP];
+      splitp<NP>(lo, l);
+      splitp<NP>(hi, h);
       const uint32_t o = boff(kr + G::KR * j, fc >> 1) + 8 * (fc & 1);
-      *reinterpret_cast<u2*>(bimg + o) = p0;
-      *reinterpret_cast<u2*>(bimg + B_PART_BYTES + o) = p1;
-      *reinterpret_cast<u2*>(bimg + 2 * B_PART_BYTES + o) = p2;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        u2 v;
+        v.x = l[p], v.y = h[p];
+        *reinterpret_cast<u2*>(bimg + p * B_PART_BYTES + o) = v;
+      }
     }
   };
 
@@ -258,20 +307,20 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
   const int g16 = lane >> 4, i16 = lane & 15, hh = lane >> 5;
   // tr read: lane 4q + p of its 16-lane group reads row r0 + q, columns c0 + 4p .. (c0 = 16 (g16 & 1))
   const int trq = i16 >> 2, trp = i16 & 3;
-  auto read_step = [&](int buf, int ksl, bf8 (&af)[2][3], bf8 (&bf)[2][3]) {
+  auto read_step = [&](int buf, int ksl, bf8 (&af)[2][NP], bf8 (&bf)[2][NP]) {
     const char* base = ldsb + buf * BUF_BYTES;
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        const int pc = ((2 * wm + mi) * 2 + ksl) * 3 + p;
+      for (int p = 0; p < NP; ++p) {
+        const int pc = ((2 * wm + mi) * 2 + ksl) * NP + p;
         af[mi][p] = __builtin_bit_cast(bf8, *reinterpret_cast<const u4*>(base + pc * 1024 + lane * 16));
       }
     const char* bimg = base + A_BYTES;
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
         s4 v[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -306,7 +355,7 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
             ldsb + A_BYTES + boff(8 * qq + 4 * t + trq, (64 * wn + 16 * ni) / 8 + (trp >> 1)) + 8 * (trp & 1));
     const int aslot = (r16 + 32 * (qq & 1)) * 16;
     const uint32_t abase0 =
-        (uint32_t)reinterpret_cast<uintptr_t>(ldsb + aslot + ((4 * wm + (qq >> 1)) * 3) * 1024);
+        (uint32_t)reinterpret_cast<uintptr_t>(ldsb + aslot + ((4 * wm + (qq >> 1)) * NP) * 1024);
     Acc2s acc[4][4];
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
@@ -327,22 +376,23 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
         // every fragment read by inline asm (the transposing-read builtin carries no memory operand, so
         // hipcc would wait for the LDS-DMA issued below, which fills the other buffer) with counted
         // waits, in the order the MFMAs need them: A row 0, B columns 0..3, then A row mi + 1 under row
-        // mi's MFMAs (lgkmcnt holds at most 15).  2-3 % over one wait for all of them.
+        // mi's MFMAs (lgkmcnt holds at most 15).  2-3 % over one wait for all of them.  A row is NP
+        // reads and a B column 2 NP, so every count below scales with NP.
         const uint32_t ab = abase0 + (uint32_t)(buf * BUF_BYTES);
-        u4 ar[2][3];
-        s4 v[4][3][2];
-        auto read_a16 = [&](int mi, u4 (&r)[3]) {
+        u4 ar[2][NP];
+        s4 v[4][NP][2];
+        auto read_a16 = [&](int mi, u4 (&r)[NP]) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p)
+          for (int p = 0; p < NP; ++p)
             asm volatile("ds_read_b128 %0, %1 offset:%2"
                          : "=v"(r[p])
-                         : "v"(ab), "i"((mi >> 1) * 6144 + p * 1024 + 256 * (mi & 1)));
+                         : "v"(ab), "i"((mi >> 1) * 2048 * NP + p * 1024 + 256 * (mi & 1)));
         };
         read_a16(0, ar[0]);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-          for (int p = 0; p < 3; ++p)
+          for (int p = 0; p < NP; ++p)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
               asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
@@ -352,31 +402,34 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
           issue_a(s + 1, buf ^ 1);
           load_b(s + 1);
         }
-        bf8 bf[4][3];
+        bf8 bf[4][NP];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
-          u4 (&cur)[3] = ar[mi & 1];
+          u4 (&cur)[NP] = ar[mi & 1];
           if (mi < 3) read_a16(mi + 1, ar[(mi + 1) & 1]);
           if (mi > 0) {
             if (mi < 3)
-              asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
+              wait_lgkm<NP>();  // row mi + 1's reads stay in flight
             else
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]));
+              wait_lgkm<0>();
+            pin<NP>(cur);
           }
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) {
             if (mi == 0) {
-              // A row 0 and B columns 0..ni landed: younger are 6 (3 - ni) B reads and A row 1's 3
-              if (ni < 2)
-                asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
+              // A row 0 and B columns 0..ni landed: younger are 2 NP (3 - ni) B reads and A row 1's NP
+              // (NP 3: 21 -> 15, 15, 9, 3)
+              if (ni == 0)
+                wait_lgkm<7 * NP>();
+              else if (ni == 1)
+                wait_lgkm<5 * NP>();
               else if (ni == 2)
-                asm volatile("s_waitcnt lgkmcnt(9)" ::: "memory");
+                wait_lgkm<3 * NP>();
               else
-                asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-              if (ni == 0) asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]));
+                wait_lgkm<NP>();
+              if (ni == 0) pin<NP>(cur);
 #pragma unroll
-              for (int p = 0; p < 3; ++p) {
+              for (int p = 0; p < NP; ++p) {
                 asm volatile("" : "+v"(v[ni][p][0]), "+v"(v[ni][p][1]));
                 u4 u;
                 u.x = __builtin_bit_cast(uint32_t, __builtin_shufflevector(v[ni][p][0], v[ni][p][0], 0, 1));
@@ -386,9 +439,10 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
                 bf[ni][p] = __builtin_bit_cast(bf8, u);
               }
             }
-            const bf8 af[3] = {__builtin_bit_cast(bf8, cur[0]), __builtin_bit_cast(bf8, cur[1]),
-                               __builtin_bit_cast(bf8, cur[2])};
-            mma6_16(af, bf[ni], acc[mi][ni]);
+            bf8 af[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) af[p] = __builtin_bit_cast(bf8, cur[p]);
+            mma6_16<NP>(af, bf[ni], acc[mi][ni]);
             if (mi == 0 || ni == 3) __builtin_amdgcn_sched_barrier(0);  // keep each wait before its MFMAs
           }
         }
@@ -462,12 +516,12 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
     }
 #pragma unroll
     for (int ksl = 0; ksl < 2; ++ksl) {
-      bf8 af[2][3], bf[2][3];
+      bf8 af[2][NP], bf[2][NP];
       read_step(buf, ksl, af, bf);
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) mma6(af[mi], bf[ni], acc[mi][ni]);
+        for (int ni = 0; ni < 2; ++ni) mma6<NP>(af[mi], bf[ni], acc[mi][ni]);
     }
   }
 
@@ -493,17 +547,23 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
   }
 }
 
-__global__ void __launch_bounds__(256, 1) gemm_nn_split_w2(Args a) { gemm_nn_split_body<2>(a); }
-__global__ void __launch_bounds__(512, 1) gemm_nn_split_w4_mf16(Args a) { gemm_nn_split_body<4, true>(a); }
+template <int NP>
+__global__ void __launch_bounds__(256, 1) gemm_nn_split_w2(Args a) {
+  gemm_nn_split_body<2, false, NP>(a);
+}
+template <int NP>
+__global__ void __launch_bounds__(512, 1) gemm_nn_split_w4_mf16(Args a) {
+  gemm_nn_split_body<4, true, NP>(a);
+}
 
 constexpr int64_t kOffMax = (int64_t)1 << 31;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
-template <int WMW, void (*K)(Args)>
+template <int WMW, int NP, void (*K)(Args)>
 hipError_t launch_w(Args a, hipStream_t st) {
-  using G = Geo<WMW>;
+  using G = Geo<WMW, NP>;
   a.mtiles = (a.M + G::TM - 1) / G::TM;
   const int64_t grid = (int64_t)a.mtiles * ((a.ncols + TN - 1) / TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
@@ -525,6 +585,7 @@ bool mf16_ok(const Args& a) {
   return e0 < kOffMax && e1 < kOffMax;
 }
 
+template <int NP>
 hipError_t launch(Args a, hipStream_t st) {
   if (a.K % BK != 0 || a.k0 % BK != 0 || a.M % 32 != 0 || a.P % 4 != 0) return hipErrorNotSupported;
   if ((int64_t)a.M * a.K * 6 >= kOffMax) return hipErrorNotSupported;
@@ -536,8 +597,13 @@ hipError_t launch(Args a, hipStream_t st) {
   int v = mrp_host::tuning().gemm_split;
   const bool mf16 = mf16_ok(a);
   if (v < 0) v = mf16 ? 7 : 2;
-  if (v == 7 && mf16) return launch_w<4, gemm_nn_split_w4_mf16>(a, st);
-  return launch_w<2, gemm_nn_split_w2>(a, st);
+  if (v == 7 && mf16) return launch_w<4, NP, gemm_nn_split_w4_mf16<NP>>(a, st);
+  return launch_w<2, NP, gemm_nn_split_w2<NP>>(a, st);
+}
+
+// parts (validated by the caller) -> the instantiation
+hipError_t launch_parts(const Args& a, int parts, hipStream_t st) {
+  return parts == 3 ? launch<3>(a, st) : parts == 2 ? launch<2>(a, st) : launch<1>(a, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -565,13 +631,13 @@ struct NTArgs {
   int32_t group;  // tile order (tile_of)
 };
 
-template <int WMW>
+template <int WMW, int NP = 3>
 struct NTGeo {
   static constexpr int TM = 64 * WMW, NW = 2 * WMW, THREADS = 64 * NW;
   static constexpr int ROWB = BK * 2;                                  // bytes per [row][32 k] bf16 row
   static constexpr int A_PART = TM * ROWB, B_PART = TN * ROWB;
-  static constexpr int BUF_BYTES = 3 * (A_PART + B_PART);
-  static constexpr int LDS_BYTES = 2 * BUF_BYTES;                      // 144 KiB at WMW 4
+  static constexpr int BUF_BYTES = NP * (A_PART + B_PART);
+  static constexpr int LDS_BYTES = 2 * BUF_BYTES;                      // 144 KiB at WMW 4, NP 3 (x NP / 3)
   static constexpr int RPP = THREADS / 8;                              // rows per load pass (8 pieces a row)
   static constexpr int AJ = TM / RPP, BJ = TN / RPP;                   // A / B pieces per thread per stage
 };
@@ -584,9 +650,9 @@ __device__ __forceinline__ uint32_t rowoff(int row, int chunk) {  // [row][4 chu
 // The products on v_mfma_f32_16x16x32_bf16 (the wave's 64 x 64 as 4 x 4 tiles of 16 x 16, one MFMA per
 // 32 k), which holds a higher clock than the 32x32x16 shape under the chip's power limit
 // (MI355X_MICROARCH.md, DVFS give-back item 7); the 32x32x16 forms are lab forms (tools/lab_forms.hip)
-template <int WMW>
+template <int WMW, int NP = 3>
 __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, int nwg) {
-  using G = NTGeo<WMW>;
+  using G = NTGeo<WMW, NP>;
   extern __shared__ u4 lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
   const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
@@ -641,17 +707,18 @@ __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, in
   auto store = [&](int buf) {
     char* base = ldsb + buf * G::BUF_BYTES;
     auto put = [&](char* img, int part_bytes, int row, const f4& v) {
-      u2 p0, p1, p2;
       f2 lo, hi;
       lo.x = v.x, lo.y = v.y, hi.x = v.z, hi.y = v.w;
-      uint32_t l0, l1, l2, h0, h1, h2;
-      split2(lo, l0, l1, l2);
-      split2(hi, h0, h1, h2);
-      p0.x = l0, p1.x = l1, p2.x = l2, p0.y = h0, p1.y = h1, p2.y = h2;
+      uint32_t l[NP], h[NP];
+      splitp<NP>(lo, l);
+      splitp<NP>(hi, h);
       const uint32_t o = rowoff(row, pc4 >> 1) + 8 * (pc4 & 1);
-      *reinterpret_cast<u2*>(img + o) = p0;
-      *reinterpret_cast<u2*>(img + part_bytes + o) = p1;
-      *reinterpret_cast<u2*>(img + 2 * part_bytes + o) = p2;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        u2 u;
+        u.x = l[p], u.y = h[p];
+        *reinterpret_cast<u2*>(img + p * part_bytes + o) = u;
+      }
     };
 #pragma unroll
     for (int j = 0; j < G::AJ; ++j) {
@@ -659,7 +726,7 @@ __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, in
       put(base, G::A_PART, r0 + G::RPP * j, areg[j]);
     }
 #pragma unroll
-    for (int j = 0; j < G::BJ; ++j) put(base + 3 * G::A_PART, G::B_PART, r0 + G::RPP * j, breg[j]);
+    for (int j = 0; j < G::BJ; ++j) put(base + NP * G::A_PART, G::B_PART, r0 + G::RPP * j, breg[j]);
   };
   // lane (r16, q) reads k = 8 q .. 8 q + 7 (chunk q) of row r16 of a 16-row block
   const int r16 = lane & 15, q = lane >> 4;
@@ -680,23 +747,23 @@ __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, in
     __builtin_amdgcn_s_barrier();
     if (s + 1 < nst) load();
     const char* base = ldsb + buf * G::BUF_BYTES;
-    const char* bb = base + 3 * G::A_PART;
-    bf8 bf[4][3];
+    const char* bb = base + NP * G::A_PART;
+    bf8 bf[4][NP];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
+      for (int p = 0; p < NP; ++p)
         bf[ni][p] = __builtin_bit_cast(bf8, *reinterpret_cast<const u4*>(bb + p * G::B_PART +
                                                                           rowoff(64 * wn + 16 * ni + r16, q)));
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-      bf8 af[3];
+      bf8 af[NP];
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
+      for (int p = 0; p < NP; ++p)
         af[p] = __builtin_bit_cast(bf8, *reinterpret_cast<const u4*>(base + p * G::A_PART +
                                                                       rowoff(64 * wm + 16 * mi + r16, q)));
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) mma6_16(af, bf[ni], acc[mi][ni]);
+      for (int ni = 0; ni < 4; ++ni) mma6_16<NP>(af, bf[ni], acc[mi][ni]);
     }
   }
   float* out = a.out + (int64_t)split * a.M * a.N;
@@ -725,8 +792,9 @@ __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, in
   }
 }
 
+template <int NP>
 __global__ void __launch_bounds__(512, 1) gemm_nt_split_w4_mf16(NTArgs a) {
-  gemm_nt_split_body<4>(a, blockIdx.x, gridDim.x);
+  gemm_nt_split_body<4, NP>(a, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -744,7 +812,10 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_split_w4_mf16(NTArgs a) {
 // (P % 16 == 0): unit ((mb KS + ks) 3 + p) 64 + lane holds lane (r = lane & 31, h = lane >> 5)'s
 // k = 16 ks + 8 h .. + 7 of row 32 mb + r, part p — `pack`'s layout.  One wave per (row block mb,
 // group of G 16-k steps); its row sums over the group go to rsum[m][group] (null: none), the two lanes
-// of a row added in one fixed order.
+// of a row added in one fixed order.  NP < 3: the image holds NP parts per (block, step) — unit
+// ((mb KS + ks) NP + p) 64 + lane, 2 NP bytes per element of g; the row sums are of the full fp32 g in
+// every form.
+template <int NP>
 __global__ void __launch_bounds__(256) split_rows(const float* __restrict__ g, int64_t gs, int32_t M, int32_t P,
                                                   int64_t KS, int32_t G, int32_t ngroups, u4* __restrict__ out,
                                                   float* __restrict__ rsum) {
@@ -759,25 +830,25 @@ __global__ void __launch_bounds__(256) split_rows(const float* __restrict__ g, i
   int64_t nd = 16 * ks0 / P;  // the step's node and first pixel (P % 16 == 0: a step is within a node)
   int px = (int)(16 * ks0 - nd * P);
   const float* row = g + (int64_t)(32 * mb + r) * P + 8 * h;
-  u4* o = out + ((int64_t)mb * KS * 3) * 64 + lane;
+  u4* o = out + ((int64_t)mb * KS * NP) * 64 + lane;
   float sum = 0.f;
 #pragma unroll 2
   for (int64_t ks = ks0; ks < ks1; ++ks) {
     const float* src = row + nd * gs + px;
     const f4 v0 = *reinterpret_cast<const f4*>(src), v1 = *reinterpret_cast<const f4*>(src + 4);
     sum += ((v0.x + v0.y) + (v0.z + v0.w)) + ((v1.x + v1.y) + (v1.z + v1.w));
-    u4 p0, p1, p2;
+    u4 pp[NP];
     const f2 x[4] = {{v0.x, v0.y}, {v0.z, v0.w}, {v1.x, v1.y}, {v1.z, v1.w}};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      uint32_t e0, e1, e2;
-      split2(x[i], e0, e1, e2);
-      p0[i] = e0, p1[i] = e1, p2[i] = e2;
+      uint32_t e[NP];
+      splitp<NP>(x[i], e);
+#pragma unroll
+      for (int p = 0; p < NP; ++p) pp[p][i] = e[p];
     }
-    u4* d = o + ks * 3 * 64;
-    __builtin_nontemporal_store(p0, d);
-    __builtin_nontemporal_store(p1, d + 64);
-    __builtin_nontemporal_store(p2, d + 128);
+    u4* d = o + ks * NP * 64;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) __builtin_nontemporal_store(pp[p], d + 64 * p);
     px += 16;
     if (px == P) {
       px = 0;
@@ -805,10 +876,17 @@ __global__ void __launch_bounds__(64) row_sums(const float* __restrict__ part, i
   if (lane == 0) out[m] = v;
 }
 
-__device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int nwg) {
-  using G = NTGeo<4>;
-  constexpr int A_BYTES = 48 * 1024;  // 256 rows x 32 k x 3 parts: 48 1-KiB pieces, 6 per wave
-  constexpr int BP = G::B_PART, BUF = A_BYTES + 3 * BP;  // 72 KiB per buffer, two buffers
+// NP: the parts kept of both operands; the image at a.ap holds NP parts per (block, step) (split_rows<NP>;
+// NP 3: `pack`'s layout)
+// (a static member of a class template, reached through the function template below: hipcc's host pass
+// drops a function template's specialization with these inline-asm immediates when a non-template
+// kernel names it — gemm_nt_psa<3>'s host stub went with it)
+template <int NP>
+struct PsaBody {
+static __device__ __forceinline__ void run(const NTArgs& a, int orig, int nwg) {
+  using G = NTGeo<4, NP>;
+  constexpr int A_BYTES = 16 * NP * 1024;  // 256 rows x 32 k x NP parts: 16 NP 1-KiB pieces, 2 NP per wave
+  constexpr int BP = G::B_PART, BUF = A_BYTES + NP * BP;  // NP 3: 72 KiB per buffer, two buffers
   extern __shared__ u4 lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
   const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
@@ -827,21 +905,21 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
   const int64_t KS = a.ktot / 16;
   const int MB = a.M / 32;
 
-  // ---- A: LDS-DMA pieces pc = (mbl 2 + ksl) 3 + p of the stage, pc = w + 8 i
+  // ---- A: LDS-DMA pieces pc = (mbl 2 + ksl) NP + p of the stage, pc = w + 8 i
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.ap);
-  uint32_t va[6];
+  uint32_t va[2 * NP];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < 2 * NP; ++i) {
     const int pc = w + 8 * i;
-    const int mbl = pc / 6, kp = pc % 6;
+    const int mbl = pc / (2 * NP), kp = pc % (2 * NP);  // kp = NP ksl + p
     const int mb = min(mt * 8 + mbl, MB - 1);  // blocks past M: any valid data, never stored
-    va[i] = (uint32_t)((((int64_t)mb * KS + kbeg / 16) * 3 + kp) * 64 + lane) * 16;
+    va[i] = (uint32_t)((((int64_t)mb * KS + kbeg / 16) * NP + kp) * 64 + lane) * 16;
   }
   auto issue_a = [&](int s, int buf) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < 2 * NP; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, lds + (buf * BUF + (w + 8 * i) * 1024) / 16, 16, va[i],
-                                               (uint32_t)s * 6 * 1024, 0, 0);
+                                               (uint32_t)s * 2 * NP * 1024, 0, 0);
   };
 
   // ---- B: thread t -> piece (t & 7) (4 pixels) of rows (t >> 3) + 64 j of the stage
@@ -872,17 +950,18 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
     char* img = ldsb + buf * BUF + A_BYTES;
 #pragma unroll
     for (int j = 0; j < G::BJ; ++j) {
-      u2 p0, p1, p2;
       f2 lo, hi;
       lo.x = breg[j].x, lo.y = breg[j].y, hi.x = breg[j].z, hi.y = breg[j].w;
-      uint32_t l0, l1, l2, h0, h1, h2;
-      split2(lo, l0, l1, l2);
-      split2(hi, h0, h1, h2);
-      p0.x = l0, p1.x = l1, p2.x = l2, p0.y = h0, p1.y = h1, p2.y = h2;
+      uint32_t l[NP], h[NP];
+      splitp<NP>(lo, l);
+      splitp<NP>(hi, h);
       const uint32_t o = rowoff(r0 + G::RPP * j, pc4 >> 1) + 8 * (pc4 & 1);
-      *reinterpret_cast<u2*>(img + o) = p0;
-      *reinterpret_cast<u2*>(img + BP + o) = p1;
-      *reinterpret_cast<u2*>(img + 2 * BP + o) = p2;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        u2 u;
+        u.x = l[p], u.y = h[p];
+        *reinterpret_cast<u2*>(img + p * BP + o) = u;
+      }
     }
   };
 
@@ -892,7 +971,7 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
   // kernel's A reads).  B: chunk qq of row 64 wn + 16 ni + r16 of the [row][32 k] images.
   const int r16 = lane & 15, qq = lane >> 4;
   const uint32_t abase0 = (uint32_t)reinterpret_cast<uintptr_t>(ldsb + (r16 + 32 * (qq & 1)) * 16 +
-                                                                 ((4 * wm + (qq >> 1)) * 3) * 1024);
+                                                                 ((4 * wm + (qq >> 1)) * NP) * 1024);
   uint32_t bro[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni)
@@ -920,19 +999,19 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
       // below would make hipcc wait for the DMA): A row 0, B columns 0..3, then A row mi + 1 under row
       // mi's MFMAs
       const uint32_t ab = abase0 + (uint32_t)(buf * BUF);
-      u4 ar[2][3], br[4][3];
-      auto read_a16 = [&](int mi, u4 (&rg)[3]) {
+      u4 ar[2][NP], br[4][NP];
+      auto read_a16 = [&](int mi, u4 (&rg)[NP]) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < NP; ++p)
           asm volatile("ds_read_b128 %0, %1 offset:%2"
                        : "=v"(rg[p])
-                       : "v"(ab), "i"((mi >> 1) * 6144 + p * 1024 + 256 * (mi & 1)));
+                       : "v"(ab), "i"((mi >> 1) * 2048 * NP + p * 1024 + 256 * (mi & 1)));
       };
       read_a16(0, ar[0]);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < NP; ++p)
           asm volatile("ds_read_b128 %0, %1 offset:%2"
                        : "=v"(br[ni][p])
                        : "v"(bro[ni] + (uint32_t)(buf * BUF)), "i"(p * BP));
@@ -942,35 +1021,38 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
       }
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
-        u4 (&cur)[3] = ar[mi & 1];
+        u4 (&cur)[NP] = ar[mi & 1];
         if (mi < 3) read_a16(mi + 1, ar[(mi + 1) & 1]);
         if (mi > 0) {
           if (mi < 3)
-            asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
+            wait_lgkm<NP>();  // row mi + 1's reads stay in flight
           else
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]));
+            wait_lgkm<0>();
+          pin<NP>(cur);
         }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           if (mi == 0) {
-            // A row 0 and B columns 0..ni landed: younger are 3 (3 - ni) B reads and A row 1's 3
+            // A row 0 and B columns 0..ni landed: younger are NP (3 - ni) B reads and A row 1's NP
+            // (NP 3: 12, 9, 6, 3)
             if (ni == 0)
-              asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
+              wait_lgkm<4 * NP>();
             else if (ni == 1)
-              asm volatile("s_waitcnt lgkmcnt(9)" ::: "memory");
+              wait_lgkm<3 * NP>();
             else if (ni == 2)
-              asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+              wait_lgkm<2 * NP>();
             else
-              asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-            if (ni == 0) asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]));
-            asm volatile("" : "+v"(br[ni][0]), "+v"(br[ni][1]), "+v"(br[ni][2]));
+              wait_lgkm<NP>();
+            if (ni == 0) pin<NP>(cur);
+            pin<NP>(br[ni]);
           }
-          const bf8 af[3] = {__builtin_bit_cast(bf8, cur[0]), __builtin_bit_cast(bf8, cur[1]),
-                             __builtin_bit_cast(bf8, cur[2])};
-          const bf8 bfr[3] = {__builtin_bit_cast(bf8, br[ni][0]), __builtin_bit_cast(bf8, br[ni][1]),
-                              __builtin_bit_cast(bf8, br[ni][2])};
-          mma6_16(af, bfr, acc[mi][ni]);
+          bf8 af[NP], bfr[NP];
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            af[p] = __builtin_bit_cast(bf8, cur[p]);
+            bfr[p] = __builtin_bit_cast(bf8, br[ni][p]);
+          }
+          mma6_16<NP>(af, bfr, acc[mi][ni]);
           if (mi == 0 || ni == 3) __builtin_amdgcn_sched_barrier(0);  // keep each wait before its MFMAs
         }
       }
@@ -990,14 +1072,23 @@ __device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int 
       }
   }
 }
+};
+template <int NP>
+__device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int nwg) {
+  PsaBody<NP>::run(a, orig, nwg);
+}
 
-__global__ void __launch_bounds__(512, 1) gemm_nt_psa(NTArgs a) { gemm_nt_psa_body(a, blockIdx.x, gridDim.x); }
+template <int NP>
+__global__ void __launch_bounds__(512, 1) gemm_nt_psa(NTArgs a) {
+  gemm_nt_psa_body<NP>(a, blockIdx.x, gridDim.x);
+}
 
 // the same with the first product's A operand pre-split (gemm_nt_psa_body: the edge encoder's W2^T,
 // packed once per weight version) — the split body re-split it once per column tile and call
+// (the encoder's kernels keep all three parts)
 __global__ void __launch_bounds__(512, 1) gemm_nt_dual_psa1(NTArgs a1, NTArgs a2, int grid1) {
   if ((int)blockIdx.x < grid1)
-    gemm_nt_psa_body(a1, blockIdx.x, grid1);
+    gemm_nt_psa_body<3>(a1, blockIdx.x, grid1);
   else
     gemm_nt_split_body<4>(a2, blockIdx.x - grid1, gridDim.x - grid1);
 }
@@ -1072,9 +1163,11 @@ extern "C" int mrp_compress_split_pack(const float* w, int64_t ld, int32_t trans
   return hipGetLastError();
 }
 
-extern "C" int mrp_compress_fwd_split(const float* x, int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
-                                      int32_t num_nodes, int32_t C, int32_t P, const void* packed_w, const float* bias,
-                                      float* y, int64_t y_node_stride, void* stream) {
+extern "C" int mrp_compress_fwd_split_p(const float* x, int64_t x_node_stride, const float* agg,
+                                        int64_t agg_node_stride, int32_t num_nodes, int32_t C, int32_t P,
+                                        const void* packed_w, const float* bias, float* y, int64_t y_node_stride,
+                                        int32_t parts, void* stream) {
+  if (parts < 1 || parts > 3) return hipErrorInvalidValue;
   if (num_nodes < 0 || C < 0 || P < 0) return hipErrorInvalidValue;
   if (num_nodes == 0 || C == 0 || P == 0) return hipSuccess;
   const int64_t plane = (int64_t)C * P;
@@ -1100,12 +1193,20 @@ extern "C" int mrp_compress_fwd_split(const float* x, int64_t x_node_stride, con
   a.k0 = C;
   a.m0 = C;
   a.P = P;
-  return launch(a, static_cast<hipStream_t>(stream));
+  return launch_parts(a, parts, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int mrp_compress_bwd_data_split(const float* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C,
-                                           int32_t P, const void* packed_wt, float* gx, int64_t gx_node_stride,
-                                           float* gagg, int64_t gagg_node_stride, void* stream) {
+extern "C" int mrp_compress_fwd_split(const float* x, int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
+                                      int32_t num_nodes, int32_t C, int32_t P, const void* packed_w, const float* bias,
+                                      float* y, int64_t y_node_stride, void* stream) {
+  return mrp_compress_fwd_split_p(x, x_node_stride, agg, agg_node_stride, num_nodes, C, P, packed_w, bias, y,
+                                  y_node_stride, 3, stream);
+}
+
+extern "C" int mrp_compress_bwd_data_split_p(const float* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C,
+                                             int32_t P, const void* packed_wt, float* gx, int64_t gx_node_stride,
+                                             float* gagg, int64_t gagg_node_stride, int32_t parts, void* stream) {
+  if (parts < 1 || parts > 3) return hipErrorInvalidValue;
   if (num_nodes < 0 || C < 0 || P < 0) return hipErrorInvalidValue;
   if (num_nodes == 0 || C == 0 || P == 0) return hipSuccess;
   const int64_t plane = (int64_t)C * P;
@@ -1131,7 +1232,14 @@ extern "C" int mrp_compress_bwd_data_split(const float* gy, int64_t gy_node_stri
   a.k0 = C;
   a.m0 = C;
   a.P = P;
-  return launch(a, static_cast<hipStream_t>(stream));
+  return launch_parts(a, parts, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mrp_compress_bwd_data_split(const float* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C,
+                                           int32_t P, const void* packed_wt, float* gx, int64_t gx_node_stride,
+                                           float* gagg, int64_t gagg_node_stride, void* stream) {
+  return mrp_compress_bwd_data_split_p(gy, gy_node_stride, num_nodes, C, P, packed_wt, gx, gx_node_stride, gagg,
+                                       gagg_node_stride, 3, stream);
 }
 
 namespace {
@@ -1147,10 +1255,31 @@ int64_t nt_workspace(int64_t M, int64_t N, int64_t ktot) {
   return ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
 }
 
+// one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
+template <int NP>
+hipError_t launch_nt(const NTArgs& a, int64_t grid, hipStream_t st) {
+  using G = NTGeo<4, NP>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_w4_mf16<NP>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(gemm_nt_split_w4_mf16<NP>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
+  return hipGetLastError();
+}
+
+template <int NP>
+hipError_t launch_psa(const NTArgs& a, int64_t grid, hipStream_t st) {
+  using G = NTGeo<4, NP>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_psa<NP>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(gemm_nt_psa<NP>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
+  return hipGetLastError();
+}
+
 // out (M x N) = sum_k g[m][k] s[n][k] (+ row sums of g into outb), k = (node, pixel) over `nodes` nodes of
-// P pixels; a.g/gs, a.s0/s0s, a.s1/s1s, a.n0, a.P set by the caller
+// P pixels; a.g/gs, a.s0/s0s, a.s1/s1s, a.n0, a.P set by the caller; parts = the bf16 parts kept (1..3)
 hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, float* outb, void* workspace,
-                  int64_t workspace_bytes, hipStream_t st) {
+                  int64_t workspace_bytes, hipStream_t st, int parts = 3) {
   using G = NTGeo<4>;
   a.mtiles = (int32_t)((M + G::TM - 1) / G::TM);
   a.ntiles = (int32_t)((N + TN - 1) / TN);
@@ -1168,12 +1297,8 @@ hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, flo
   // the 32-k-stage form on 16x16x32 MFMAs (split_nt 3; the compress weight gradient takes nt_run_psa
   // instead at 4, and at -1 where C >= 1024).  Round 4's 32x32x16 forms (the 32-k-stage one and the
   // pipelined 16-k-stage one), 4-5 % slower at every config shape, are lab forms (tools/lab_forms.hip).
-  static const hipError_t attr16 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_w4_mf16),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr16 != hipSuccess) return attr16;
   a.group = mrp_host::tuning().nt_group;
-  hipLaunchKernelGGL(gemm_nt_split_w4_mf16, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = parts == 3 ? launch_nt<3>(a, grid, st) : parts == 2 ? launch_nt<2>(a, grid, st) : launch_nt<1>(a, grid, st);
   if (e != hipSuccess || ns == 1) return e;
   const int64_t n4 = M * N / 4;
   const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
@@ -1221,7 +1346,7 @@ PsaPlan psa_plan(int64_t M, int64_t N, int64_t ktot) {
 // image `img` (split_rows' layout, or written by the data gradient: mrp_compress_bwd_data_split_img);
 // the workspace holds the partial tiles when the plan splits K
 hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* rparts, int nparts, float* out,
-                    float* outb, void* tiles_ws, hipStream_t st) {
+                    float* outb, void* tiles_ws, hipStream_t st, int parts) {
   using G = NTGeo<4>;
   const PsaPlan q = psa_plan(M, N, a.ktot);
   a.ap = img;
@@ -1234,12 +1359,8 @@ hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* 
   a.N = (int32_t)N;
   const int64_t grid = (int64_t)a.mtiles * a.ntiles * q.ns;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_psa),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
   a.group = mrp_host::tuning().nt_group;
-  hipLaunchKernelGGL(gemm_nt_psa, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = parts == 3 ? launch_psa<3>(a, grid, st) : parts == 2 ? launch_psa<2>(a, grid, st) : launch_psa<1>(a, grid, st);
   if (e != hipSuccess) return e;
   if (outb != nullptr) {
     hipLaunchKernelGGL(row_sums, dim3((unsigned)M), dim3(64), 0, st, rparts, nparts, (int32_t)M, outb);
@@ -1253,8 +1374,10 @@ hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* 
   return hipGetLastError();
 }
 
+// (the plan, and so the workspace layout and bound, is the same for every part count: a reduced form's
+// image, 2 parts bytes per element, fills the front of the six-byte one's room)
 hipError_t nt_run_psa(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, float* outb, void* workspace,
-                      int64_t workspace_bytes, hipStream_t st) {
+                      int64_t workspace_bytes, hipStream_t st, int parts) {
   a.ktot = (int64_t)nodes * a.P;
   const PsaPlan q = psa_plan(M, N, a.ktot);
   if (workspace == nullptr || workspace_bytes < q.bytes || !aligned16(workspace)) return hipErrorInvalidValue;
@@ -1262,11 +1385,20 @@ hipError_t nt_run_psa(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out,
   u4* img = reinterpret_cast<u4*>(ws + q.img_off);
   float* rs = reinterpret_cast<float*>(ws + q.rs_off);
   const int64_t waves = (M / 32) * q.ngroups;
-  hipLaunchKernelGGL(split_rows, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P,
-                     a.ktot / 16, q.G, q.ngroups, img, outb != nullptr ? rs : nullptr);
+  const dim3 sgrid((unsigned)((waves + 3) / 4));
+  float* rsp = outb != nullptr ? rs : nullptr;
+  if (parts == 3)
+    hipLaunchKernelGGL(split_rows<3>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
+                       img, rsp);
+  else if (parts == 2)
+    hipLaunchKernelGGL(split_rows<2>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
+                       img, rsp);
+  else
+    hipLaunchKernelGGL(split_rows<1>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
+                       img, rsp);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return psa_gemm(a, M, N, img, rs, q.ngroups, out, outb, ws, st);
+  return psa_gemm(a, M, N, img, rs, q.ngroups, out, outb, ws, st, parts);
 }
 
 }  // namespace
@@ -1278,10 +1410,12 @@ extern "C" int64_t mrp_compress_bwd_weight_split_workspace(int32_t num_nodes, in
   return nt_workspace(C, 2 * (int64_t)C, ktot);
 }
 
-extern "C" int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_stride, const float* x,
-                                             int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
-                                             int32_t num_nodes, int32_t C, int32_t P, float* gw, float* gbias,
-                                             void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int mrp_compress_bwd_weight_split_p(const float* gy, int64_t gy_node_stride, const float* x,
+                                               int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
+                                               int32_t num_nodes, int32_t C, int32_t P, float* gw, float* gbias,
+                                               void* workspace, int64_t workspace_bytes, int32_t parts,
+                                               void* stream) {
+  if (parts < 1 || parts > 3) return hipErrorInvalidValue;
   if (num_nodes < 0 || C < 0 || P < 0) return hipErrorInvalidValue;
   if (C == 0) return hipSuccess;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1308,8 +1442,16 @@ extern "C" int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_st
   a.n0 = C;
   a.P = P;
   if (psa_ok(M, (int64_t)num_nodes * P))
-    return nt_run_psa(a, M, N, num_nodes, gw, gbias, workspace, workspace_bytes, st);
-  return nt_run(a, M, N, num_nodes, gw, gbias, workspace, workspace_bytes, st);
+    return nt_run_psa(a, M, N, num_nodes, gw, gbias, workspace, workspace_bytes, st, parts);
+  return nt_run(a, M, N, num_nodes, gw, gbias, workspace, workspace_bytes, st, parts);
+}
+
+extern "C" int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_stride, const float* x,
+                                             int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
+                                             int32_t num_nodes, int32_t C, int32_t P, float* gw, float* gbias,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+  return mrp_compress_bwd_weight_split_p(gy, gy_node_stride, x, x_node_stride, agg, agg_node_stride, num_nodes, C, P,
+                                         gw, gbias, workspace, workspace_bytes, 3, stream);
 }
 
 // The edge encoder's backward GEMMs on the same kernel (training path, encoder.py): operands are rows
@@ -1430,9 +1572,9 @@ __global__ void __launch_bounds__(256) dzT_pack(const float* __restrict__ dz, in
 // both products with a pre-split A: W2^T's packed image and dz^T's (dzT_pack)
 __global__ void __launch_bounds__(512, 1) gemm_nt_dual_psa2(NTArgs a1, NTArgs a2, int grid1) {
   if ((int)blockIdx.x < grid1)
-    gemm_nt_psa_body(a1, blockIdx.x, grid1);
+    gemm_nt_psa_body<3>(a1, blockIdx.x, grid1);
   else
-    gemm_nt_psa_body(a2, blockIdx.x - grid1, gridDim.x - grid1);
+    gemm_nt_psa_body<3>(a2, blockIdx.x - grid1, gridDim.x - grid1);
 }
 
 struct EncPlan {

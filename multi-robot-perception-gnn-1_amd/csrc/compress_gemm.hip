@@ -41,13 +41,13 @@
 
 #include <type_traits>
 
+#include "gemm_common.hpp"
 #include "mrp_gnn.h"
 #include "tuning.hpp"
 
 namespace mrp_cg {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
+using namespace mrp_gemm;  // vector types, rsrc, xcd_remap, the split-K host helpers: gemm_common.hpp
 
 template <int MF_, int BK_, int NBUF_, int WM_, int WN_, int WT_ = 64>
 struct Cfg {
@@ -78,24 +78,12 @@ struct Cfg {
 // are no longer built.
 using V1 = Cfg<32, 32, 2, 2, 2>;
 
-// Buffer resource over `base` (raw, offsets in bytes; the range check is never reached: every lane
-// offset is clamped into its tensor on the host side of the kernel)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
-}
-
 // One 1 KiB LDS-DMA piece: lane l's 16 bytes from base + voff + soff land at lds + 16 l.  The
 // per-lane part (voff) is fixed for the whole K loop, the per-stage advance is the scalar soff.
+// (The buffer resource's range check is never reached: every lane offset is clamped into its tensor
+// on the host side of the kernel.)
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, f4* lds, uint32_t voff, uint32_t soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, lds, 16, voff, soff, 0, 0);
-}
-
-// Bijective block -> work-item remap: blocks orig, orig + 8, ... run on the same XCD (the dispatcher
-// deals blocks round-robin over the 8 XCDs) and get consecutive ids, so tiles that share an operand
-// share that XCD's L2 (cdna_hip_programming.md, XCD swizzle).
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
 }
 
 template <int BK>
@@ -552,23 +540,6 @@ __global__ void __launch_bounds__(G::THREADS, G::WG_PER_CU) gemm_nt(NTArgs a) {
   }
 }
 
-__global__ void __launch_bounds__(256) split_sum(const f4* __restrict__ part, int nsplit, int64_t n4, f4* __restrict__ out,
-                                                 const float* __restrict__ partb, int32_t M, float* __restrict__ outb) {
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t e = tid; e < n4; e += stride) {
-    f4 v = part[e];
-    for (int s = 1; s < nsplit; ++s) v += part[(int64_t)s * n4 + e];
-    out[e] = v;
-  }
-  if (outb != nullptr)
-    for (int64_t m = tid; m < M; m += stride) {
-      float v = partb[m];
-      for (int s = 1; s < nsplit; ++s) v += partb[(int64_t)s * M + m];
-      outb[m] = v;
-    }
-}
-
 // wt (cols x rows) = w^T for w (rows x cols), 32 x 32 tiles through LDS
 __global__ void __launch_bounds__(256) transpose(const float* __restrict__ w, float* __restrict__ wt, int32_t rows, int32_t cols) {
   __shared__ float tile[32][33];
@@ -587,10 +558,7 @@ __global__ void __launch_bounds__(256) transpose(const float* __restrict__ w, fl
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 constexpr int kCUs = 256;
-constexpr int64_t kOffMax = (int64_t)1 << 31;  // buffer offsets are 32-bit; keep every one below 2^31
 
 template <class G>
 hipError_t launch_nn_cfg(NNArgs a, hipStream_t st) {
@@ -757,8 +725,7 @@ extern "C" int64_t mrp_compress_bwd_weight_workspace(int32_t num_nodes, int32_t 
   const int64_t M = C, N = 2 * (int64_t)C;
   const int64_t stride = max_node_stride > (int64_t)C * P ? max_node_stride : (int64_t)C * P;
   const SplitPlan sp = plan_nt_any(M, N, (int64_t)num_nodes * P, P, stride);
-  if (sp.nsplit <= 1) return 0;
-  return ((int64_t)sp.nsplit * M * N + (int64_t)sp.nsplit * M) * 4;
+  return splitk_place(sp.nsplit, M, N).bytes;
 }
 
 extern "C" int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, const float* x, int64_t x_node_stride,
@@ -783,9 +750,8 @@ extern "C" int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, 
   const int64_t ktot = (int64_t)num_nodes * P;
   const SplitPlan sp = plan_nt_any(M, N, ktot, P, max3(gy_node_stride, x_node_stride, agg_node_stride));
   if (sp.nsplit == 0) return hipErrorNotSupported;  // P % BK, or node strides beyond 32-bit offsets
-  const int64_t need = sp.nsplit == 1 ? 0 : ((int64_t)sp.nsplit * M * N + (int64_t)sp.nsplit * M) * 4;
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need || !aligned16(workspace))) return hipErrorInvalidValue;
-  float* ws = static_cast<float*>(workspace);
+  const SplitK pl = splitk_place(sp.nsplit, M, N, gw, gbias, workspace, workspace_bytes);
+  if (pl.err != hipSuccess) return pl.err;
   NTArgs a = {};
   a.g = gy;
   a.gs = gy_node_stride;
@@ -793,8 +759,8 @@ extern "C" int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, 
   a.s0s = x_node_stride;
   a.s1 = agg;
   a.s1s = agg_node_stride;
-  a.out = sp.nsplit == 1 ? gw : ws;
-  a.outb = gbias == nullptr ? nullptr : (sp.nsplit == 1 ? gbias : ws + sp.nsplit * M * N);
+  a.out = pl.out;
+  a.outb = pl.outb;
   a.ktot = ktot;
   a.kchunk = sp.kchunk;
   a.M = (int32_t)M;
@@ -803,11 +769,7 @@ extern "C" int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, 
   a.P = P;
   hipError_t e = launch_nt(a, sp.nsplit, st);
   if (e != hipSuccess || sp.nsplit == 1) return e;
-  const int64_t n4 = M * N / 4;  // N = 2C, C % 4 == 0
-  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-  hipLaunchKernelGGL(split_sum, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(ws), sp.nsplit, n4,
-                     reinterpret_cast<f4*>(gw), a.outb, (int32_t)M, gbias);
-  return hipGetLastError();
+  return split_sum(pl.out, sp.nsplit, M, N, gw, pl.outb, sp.nsplit, gbias, st);  // M N % 4 == 0: N = 2C, C % 8 == 0
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -15,9 +15,10 @@
 // three-way split removed: one v_mfma_f32_16x16x32_{bf16,f16} per product instead of six, one operand
 // image instead of three, one accumulator set instead of hi + lo, half the bytes.  Same workgroup (8
 // waves, a 256 x 128 output tile as 4 x 2 waves of 64 x 64), same 32-k stages in two LDS buffers with one
-// barrier per stage, same XCD-aware tile_of order, same packed-weight layout (`pack`'s, 2 bytes per
-// element, one part) arriving by LDS-DMA, same XOR-swizzled row-major activation image read back with
-// ds_read_b64_tr_b16 (NN) and the same rotated [row][32 k] images read with ds_read_b128 (NT).
+// barrier per stage, same XCD-aware tile_of order (gemm_common.hpp, with the image offsets boff and
+// rowoff), same packed-weight layout (`pack`'s, 2 bytes per element, one part) arriving by LDS-DMA, same
+// XOR-swizzled row-major activation image read back with ds_read_b64_tr_b16 (NN) and the same rotated
+// [row][32 k] images read with ds_read_b128 (NT).
 //
 // NN epilogue: the MFMA's operand roles are the fp32 kernel's (weight rows x activation columns), so a
 // lane's four accumulator registers are four channels of one pixel and each is one 2-byte
@@ -32,12 +33,7 @@
 #include "mrp_gnn.h"
 #include "tuning.hpp"
 
-namespace mrp_cs {
-// compress_split.hip: the split-K planner of the weight-gradient kernels (256 x 128 tiles, 32-k stages)
-int nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk);
-}  // namespace mrp_cs
-
-namespace mrp_ch {  // types, tile sizes, LDS layouts and the tile order: compress_half_common.hpp
+namespace mrp_ch {  // types, tile sizes, the weight side, LDS layouts and the tile order: compress_half_common.hpp
 
 // A (M x K) = w (row-major, stride lda) or w^T (w: K x M row-major, stride lda), rounded to T, in
 // compress_split.hip's `pack` layout with one part: 16-byte unit (mb KS + ks) 64 + lane holds lane
@@ -79,9 +75,8 @@ template <typename T>
 __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
   __shared__ u4 lds[LDS_BYTES / 16];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+  const int nwg = gridDim.x;
+  const int id = xcd_remap(blockIdx.x, nwg);
   int mt, nt;
   tile_of(id, a.mtiles, nwg / a.mtiles, a.group, mt, nt);
   const int64_t nbase = (int64_t)nt * TN;
@@ -90,22 +85,8 @@ __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
   const int wm = w >> 1, wn = w & 1;
   const int KS = a.K / 16, nst = a.K / BK, ks0 = a.k0 / BK, MB = a.M / 32;
 
-  // ---- A: LDS-DMA pieces pc = 2 mbl + ksl (local 32-row block, 16-k step), pc = w and w + 8
-  const __amdgpu_buffer_rsrc_t ra = rsrc(a.ap);
-  uint32_t va[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int pc = w + 8 * i;
-    const int mbl = pc >> 1, ksl = pc & 1;
-    const int mb = min(mt * (TM / 32) + mbl, MB - 1);  // blocks past M: any valid data, never stored
-    va[i] = (uint32_t)((((int64_t)mb * KS + ksl) * 64 + lane) * 16);
-  }
-  auto issue_a = [&](int s, int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, lds + (buf * BUF_BYTES + (w + 8 * i) * 1024) / 16, 16, va[i],
-                                               (uint32_t)s * 2 * 1024, 0, 0);
-  };
+  // ---- A: the packed weight by LDS-DMA, its fragments by ds_read_b128 (compress_half_common.hpp)
+  const WeightSide wa(a.ap, lds, mt, MB, KS, lane, w);
 
   // ---- B: thread t loads the 16-byte piece (row t >> 4, columns 8 (t & 15) ..) of a stage
   const int fc = threadIdx.x & 15, kr = threadIdx.x >> 4;
@@ -121,10 +102,8 @@ __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
   };
   const uint32_t bst = A_BYTES + boff(kr, fc);
 
-  // ---- fragments: lane (r16, qq) of a 16 x 16 tile holds k = 8 qq .. 8 qq + 7.  A: 16-row block mi of the
-  // wave is half (mi & 1) of 32-row block 2 wm + (mi >> 1); the image holds 16-k steps in `pack`'s lane order
-  // (lane r + 32 h: row r, k 8 h ..), so the lane reads step qq >> 1, slot 16 (mi & 1) + r16 + 32 (qq & 1).
-  // B: the transposing reads of rows 8 qq + 4 t .. + 3 (t = 0, 1), columns 64 wn + 16 ni ...
+  // ---- B fragments: lane (r16, qq) of a 16 x 16 tile holds k = 8 qq .. 8 qq + 7: the transposing reads of
+  // rows 8 qq + 4 t .. + 3 (t = 0, 1), columns 64 wn + 16 ni ...
   const int r16 = lane & 15, qq = lane >> 4;
   const int trq = r16 >> 2, trp = r16 & 3;
   uint32_t tr16[4][2];
@@ -134,15 +113,10 @@ __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
     for (int t = 0; t < 2; ++t)
       tr16[ni][t] = (uint32_t)reinterpret_cast<uintptr_t>(
           ldsb + A_BYTES + boff(8 * qq + 4 * t + trq, (64 * wn + 16 * ni) / 8 + (trp >> 1)) + 8 * (trp & 1));
-  const uint32_t abase0 =
-      (uint32_t)reinterpret_cast<uintptr_t>(ldsb + (r16 + 32 * (qq & 1)) * 16 + (4 * wm + (qq >> 1)) * 1024);
   f4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
-  issue_a(0, 0);
+  wa.issue(0, 0);
   load_b(0);
 #pragma unroll 1
   for (int s = 0; s < nst; ++s) {
@@ -157,18 +131,14 @@ __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
     const uint32_t bo = (uint32_t)(buf * BUF_BYTES);
     u4 ar[4];
     s4 v[4][2];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-      asm volatile("ds_read_b128 %0, %1 offset:%2"
-                   : "=v"(ar[mi])
-                   : "v"(abase0 + bo), "i"((mi >> 1) * 2048 + 256 * (mi & 1)));
+    wa.read(bo, ar);
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
       for (int t = 0; t < 2; ++t)
         asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v[ni][t]) : "v"(tr16[ni][t] + bo));
     if (s + 1 < nst) {
-      issue_a(s + 1, buf ^ 1);
+      wa.issue(s + 1, buf ^ 1);
       load_b(s + 1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -176,8 +146,7 @@ __global__ void __launch_bounds__(THREADS) gemm_nn_half(Args a) {
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       asm volatile("" : "+v"(v[ni][0]), "+v"(v[ni][1]));
-      const u2 lo = __builtin_bit_cast(u2, v[ni][0]), hi = __builtin_bit_cast(u2, v[ni][1]);
-      bf[ni] = u4{lo.x, lo.y, hi.x, hi.y};
+      bf[ni] = join_tr(v[ni][0], v[ni][1]);
     }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
@@ -254,9 +223,7 @@ template <typename T>
 __global__ void __launch_bounds__(THREADS) gemm_nt_half(NTArgs a) {
   __shared__ u4 lds[LDS_BYTES / 16];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + orig / 8;
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int tiles = a.mtiles * a.ntiles;
   const int split = id / tiles, tid = id - split * tiles;
   int mt, nt;
@@ -312,10 +279,7 @@ __global__ void __launch_bounds__(THREADS) gemm_nt_half(NTArgs a) {
     bro[i] = (uint32_t)reinterpret_cast<uintptr_t>(ldsb + A_BYTES + rowoff(64 * wn + 16 * i + r16, qq));
   }
   f4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   if (nst > 0) load();
 #pragma unroll 1
   for (int s = 0; s < nst; ++s) {
@@ -339,20 +303,7 @@ __global__ void __launch_bounds__(THREADS) gemm_nt_half(NTArgs a) {
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = T::mma(ar[mi], br[ni], acc[mi][ni]);
   }
-  // register r of lane (r16, qq) of tile (mi, ni): row 16 mi + 4 qq + r, column 16 ni + r16
-  float* out = a.out + (int64_t)split * a.M * a.N;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = nbase + 64 * wn + 16 * ni + r16;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = mbase + 64 * wm + 16 * mi + 4 * qq + r;
-        if (m < a.M) out[(int64_t)m * a.N + n] = acc[mi][ni][r];
-      }
-  }
+  store_partial(acc, a.out + (int64_t)split * a.M * a.N, a.M, a.N, mbase + 64 * wm, nbase + 64 * wn, r16, qq);
   if (a.outb != nullptr && nt == 0) {  // the column-tile-0 workgroups write the split's row sums
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -365,30 +316,6 @@ __global__ void __launch_bounds__(THREADS) gemm_nt_half(NTArgs a) {
   }
 }
 
-// out = sum over the splits of part (fixed order); outb = the same over the row-sum partials
-// (compress_split.hip's split_sum_nt)
-__global__ void __launch_bounds__(256) split_sum(const f4* __restrict__ part, int nsplit, int64_t n4,
-                                                 f4* __restrict__ out, const float* __restrict__ partb, int32_t M,
-                                                 float* __restrict__ outb) {
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t e = tid; e < n4; e += stride) {
-    f4 v = part[e];
-    for (int s = 1; s < nsplit; ++s) v += part[(int64_t)s * n4 + e];
-    out[e] = v;
-  }
-  if (outb != nullptr)
-    for (int64_t m = tid; m < M; m += stride) {
-      float v = partb[m];
-      for (int s = 1; s < nsplit; ++s) v += partb[(int64_t)s * M + m];
-      outb[m] = v;
-    }
-}
-
-constexpr int64_t kOffMax = (int64_t)1 << 31;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool is_half(int32_t dtype) { return dtype == MRP_DTYPE_BF16 || dtype == MRP_DTYPE_F16; }
 bool native_on() { return mrp_host::tuning().compress_half != 0; }
 
 hipError_t launch_nn(int32_t dtype, Args a, hipStream_t st) {
@@ -402,23 +329,7 @@ hipError_t launch_nn(int32_t dtype, Args a, hipStream_t st) {
   const int64_t grid = (int64_t)a.mtiles * ((a.ncols + TN - 1) / TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   a.group = mrp_host::tuning().gemm_group;
-  if (dtype == MRP_DTYPE_BF16)
-    hipLaunchKernelGGL(gemm_nn_half<BF16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(gemm_nn_half<F16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-// splits of K = nodes P (whole 32-k stages): compress_split.hip's planner, or the count the
-// "half_nt_splits" knob forces (clamped so that no split is empty)
-int plan_splits(int64_t M, int64_t N, int64_t ktot, int64_t* kchunk) {
-  const int64_t tiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-  const int forced = mrp_host::tuning().half_nt_splits;
-  if (forced <= 0) return mrp_cs::nt_splits(tiles, ktot, M, N, kchunk);
-  const int64_t stages = ktot / BK;
-  const int64_t per = (stages + forced - 1) / forced;
-  *kchunk = per * BK;
-  return (int)((stages + per - 1) / per);
+  return launch_t(dtype, gemm_nn_half<BF16>, gemm_nn_half<F16>, dim3((unsigned)grid), dim3(THREADS), st, a);
 }
 
 }  // namespace mrp_ch
@@ -437,13 +348,8 @@ extern "C" int mrp_compress_pack_t(int32_t dtype, const float* w, int64_t ld, in
   if (!w || !packed || !aligned16(packed) || ld < (transpose ? M : K)) return hipErrorInvalidValue;
   if (M % 32 != 0 || K % 32 != 0) return hipErrorNotSupported;
   const int64_t threads = (int64_t)(M / 32) * (K / 16) * 64;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  if (dtype == MRP_DTYPE_BF16)
-    hipLaunchKernelGGL(pack_t<BF16>, grid, dim3(256), 0, st, w, ld, transpose ? 1 : 0, M, K, static_cast<u4*>(packed));
-  else
-    hipLaunchKernelGGL(pack_t<F16>, grid, dim3(256), 0, st, w, ld, transpose ? 1 : 0, M, K, static_cast<u4*>(packed));
-  return hipGetLastError();
+  return launch_t(dtype, pack_t<BF16>, pack_t<F16>, dim3((unsigned)((threads + 255) / 256)), dim3(256),
+                  static_cast<hipStream_t>(stream), w, ld, transpose ? 1 : 0, M, K, static_cast<u4*>(packed));
 }
 
 extern "C" int mrp_compress_fwd_t(int32_t dtype, const void* x, int64_t x_node_stride, const void* agg,
@@ -516,8 +422,8 @@ extern "C" int64_t mrp_compress_bwd_weight_t_workspace(int32_t num_nodes, int32_
   if (num_nodes <= 0 || C <= 0 || P <= 0 || C % 32 != 0 || P % BK != 0) return 0;
   const int64_t M = C, N = 2 * (int64_t)C;
   int64_t kchunk;
-  const int ns = plan_splits(M, N, (int64_t)num_nodes * P, &kchunk);
-  return ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
+  const int ns = plan_splits(M, N, (int64_t)num_nodes * P, mrp_host::tuning().half_nt_splits, &kchunk);
+  return splitk_place(ns, M, N).bytes;
 }
 
 extern "C" int mrp_compress_bwd_weight_t(int32_t dtype, const void* gy, int64_t gy_node_stride, const void* x,
@@ -549,29 +455,7 @@ extern "C" int mrp_compress_bwd_weight_t(int32_t dtype, const void* gy, int64_t 
   a.s1s = agg_node_stride;
   a.n0 = C;
   a.P = P;
-  a.M = (int32_t)M;
-  a.N = (int32_t)N;
-  a.mtiles = (int32_t)((M + TM - 1) / TM);
-  a.ntiles = (int32_t)((N + TN - 1) / TN);
   a.ktot = (int64_t)num_nodes * P;
-  const int ns = plan_splits(M, N, a.ktot, &a.kchunk);
-  const int64_t need = ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need || !aligned16(workspace))) return hipErrorInvalidValue;
-  float* ws = static_cast<float*>(workspace);
-  a.out = ns <= 1 ? gw : ws;
-  a.outb = gbias == nullptr ? nullptr : (ns <= 1 ? gbias : ws + (int64_t)ns * M * N);
-  const int64_t grid = (int64_t)a.mtiles * a.ntiles * ns;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  a.group = mrp_host::tuning().nt_group;
-  if (dtype == MRP_DTYPE_BF16)
-    hipLaunchKernelGGL(gemm_nt_half<BF16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(gemm_nt_half<F16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || ns <= 1) return e;
-  const int64_t n4 = M * N / 4;
-  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-  hipLaunchKernelGGL(split_sum, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(ws), ns, n4,
-                     reinterpret_cast<f4*>(gw), a.outb, (int32_t)M, gbias);
-  return hipGetLastError();
+  return run_wgrad(dtype, gemm_nt_half<BF16>, gemm_nt_half<F16>, a, mrp_host::tuning().half_nt_splits, M, N, gw, gbias,
+                   workspace, workspace_bytes, st);
 }

@@ -25,17 +25,12 @@
 // XOR swizzle (gy: two of them, 256 channels) and both operands' fragments come back through
 // ds_read_b64_tr_b16.  A stage may cross a node boundary (each thread walks its own row's (node, pixel));
 // rows past the split's end are zero-filled.  K = nodes P is split over workgroups into fp32 partial tiles
-// summed in a fixed order by split_sum_cl (deterministic, no atomics); db from the gy pieces widened to
+// summed in a fixed order by split_sum (deterministic, no atomics); db from the gy pieces widened to
 // fp32, per split, reduced over the stage's 32 rows through LDS in a fixed order.
 
 #include "compress_half_common.hpp"
 #include "mrp_gnn.h"
 #include "tuning.hpp"
-
-namespace mrp_cs {
-// compress_split.hip: the split-K planner of the weight-gradient kernels (256 x 128 tiles, 32-k stages)
-int nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk);
-}  // namespace mrp_cs
 
 namespace mrp_ccl {
 
@@ -61,9 +56,8 @@ template <typename T>
 __global__ void __launch_bounds__(THREADS) gemm_cl_half(Args a) {
   __shared__ u4 lds[LDS_BYTES / 16];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+  const int nwg = gridDim.x;
+  const int id = xcd_remap(blockIdx.x, nwg);
   int mt, nt;
   tile_of(id, a.mtiles, nwg / a.mtiles, a.group, mt, nt);
   const int64_t nbase = (int64_t)nt * TN;
@@ -72,22 +66,8 @@ __global__ void __launch_bounds__(THREADS) gemm_cl_half(Args a) {
   const int wm = w >> 1, wn = w & 1;
   const int KS = a.K / 16, nst = a.K / BK, ks0 = a.k0 / BK, MB = a.M / 32;
 
-  // ---- A: LDS-DMA pieces pc = 2 mbl + ksl (local 32-row block, 16-k step), pc = w and w + 8 (gemm_nn_half's)
-  const __amdgpu_buffer_rsrc_t ra = rsrc(a.ap);
-  uint32_t va[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int pc = w + 8 * i;
-    const int mbl = pc >> 1, ksl = pc & 1;
-    const int mb = min(mt * (TM / 32) + mbl, MB - 1);  // blocks past M: any valid data, never stored
-    va[i] = (uint32_t)((((int64_t)mb * KS + ksl) * 64 + lane) * 16);
-  }
-  auto issue_a = [&](int s, int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, lds + (buf * BUF_BYTES + (w + 8 * i) * 1024) / 16, 16, va[i],
-                                               (uint32_t)s * 2 * 1024, 0, 0);
-  };
+  // ---- A: the packed weight by LDS-DMA, its fragments by ds_read_b128 (compress_half_common.hpp)
+  const WeightSide wa(a.ap, lds, mt, MB, KS, lane, w);
 
   // ---- B: thread t loads the 16-byte piece (pixel row t >> 2, k 8 (t & 3) ..) of a stage
   const int pc4 = threadIdx.x & 3, prow = threadIdx.x >> 2;
@@ -103,22 +83,17 @@ __global__ void __launch_bounds__(THREADS) gemm_cl_half(Args a) {
   };
   const uint32_t bst = A_BYTES + rowoff(prow, pc4);
 
-  // ---- fragments: lane (r16, qq) of a 16 x 16 tile holds k = 8 qq .. 8 qq + 7.  A as gemm_nn_half; B: chunk
-  // qq of pixel row 64 wn + 16 ni + r16
+  // ---- B fragments: lane (r16, qq) of a 16 x 16 tile holds k = 8 qq .. 8 qq + 7: chunk qq of pixel row
+  // 64 wn + 16 ni + r16
   const int r16 = lane & 15, qq = lane >> 4;
   uint32_t bro[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni)
     bro[ni] = (uint32_t)reinterpret_cast<uintptr_t>(ldsb + A_BYTES + rowoff(64 * wn + 16 * ni + r16, qq));
-  const uint32_t abase0 =
-      (uint32_t)reinterpret_cast<uintptr_t>(ldsb + (r16 + 32 * (qq & 1)) * 16 + (4 * wm + (qq >> 1)) * 1024);
   f4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
-  issue_a(0, 0);
+  wa.issue(0, 0);
   load_b(0);
 #pragma unroll 1
   for (int s = 0; s < nst; ++s) {
@@ -132,15 +107,11 @@ __global__ void __launch_bounds__(THREADS) gemm_cl_half(Args a) {
     // for the DMA, which fills the other buffer)
     const uint32_t bo = (uint32_t)(buf * BUF_BYTES);
     u4 ar[4], bf[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-      asm volatile("ds_read_b128 %0, %1 offset:%2"
-                   : "=v"(ar[mi])
-                   : "v"(abase0 + bo), "i"((mi >> 1) * 2048 + 256 * (mi & 1)));
+    wa.read(bo, ar);
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) asm volatile("ds_read_b128 %0, %1" : "=v"(bf[ni]) : "v"(bro[ni] + bo));
     if (s + 1 < nst) {
-      issue_a(s + 1, buf ^ 1);
+      wa.issue(s + 1, buf ^ 1);
       load_b(s + 1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -235,9 +206,7 @@ template <typename T>
 __global__ void __launch_bounds__(THREADS) gemm_wg_cl_half(WArgs a) {
   __shared__ u4 lds[LDS_BYTES / 16];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + orig / 8;
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int tiles = a.mtiles * a.ntiles;
   const int split = id / tiles, tid = id - split * tiles;
   int mt, nt;
@@ -311,10 +280,7 @@ __global__ void __launch_bounds__(THREADS) gemm_wg_cl_half(WArgs a) {
           ldsb + A_BYTES + boff(krow, (64 * wn + 16 * i) / 8 + (trp >> 1)) + 8 * (trp & 1));
     }
   f4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   if (nst > 0) load();
 #pragma unroll 1
   for (int s = 0; s < nst; ++s) {
@@ -339,30 +305,15 @@ __global__ void __launch_bounds__(THREADS) gemm_wg_cl_half(WArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       asm volatile("" : "+v"(av[i][0]), "+v"(av[i][1]), "+v"(bv[i][0]), "+v"(bv[i][1]));
-      const u2 alo = __builtin_bit_cast(u2, av[i][0]), ahi = __builtin_bit_cast(u2, av[i][1]);
-      const u2 blo = __builtin_bit_cast(u2, bv[i][0]), bhi2 = __builtin_bit_cast(u2, bv[i][1]);
-      ar[i] = u4{alo.x, alo.y, ahi.x, ahi.y};
-      br[i] = u4{blo.x, blo.y, bhi2.x, bhi2.y};
+      ar[i] = join_tr(av[i][0], av[i][1]);
+      br[i] = join_tr(bv[i][0], bv[i][1]);
     }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = T::mma(ar[mi], br[ni], acc[mi][ni]);
   }
-  // register r of lane (r16, qq) of tile (mi, ni): row 16 mi + 4 qq + r, column 16 ni + r16
-  float* out = a.out + (int64_t)split * a.M * a.N;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = nbase + 64 * wn + 16 * ni + r16;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = mbase + 64 * wm + 16 * mi + 4 * qq + rg;
-        if (m < a.M) out[(int64_t)m * a.N + n] = acc[mi][ni][rg];
-      }
-  }
+  store_partial(acc, a.out + (int64_t)split * a.M * a.N, a.M, a.N, mbase + 64 * wm, nbase + 64 * wn, r16, qq);
   if (dob) {  // workgroup-uniform.  [32 stage rows][256 channels] fp32 in LDS, summed over the rows in order
     float* ldsf = reinterpret_cast<float*>(lds);
     __syncthreads();  // every wave is past its last fragment reads
@@ -381,30 +332,6 @@ __global__ void __launch_bounds__(THREADS) gemm_wg_cl_half(WArgs a) {
   }
 }
 
-// out = sum over the splits of part (fixed order); outb = the same over the db partials (compress_half.hip's
-// split_sum)
-__global__ void __launch_bounds__(256) split_sum_cl(const f4* __restrict__ part, int nsplit, int64_t n4,
-                                                    f4* __restrict__ out, const float* __restrict__ partb, int32_t M,
-                                                    float* __restrict__ outb) {
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t e = tid; e < n4; e += stride) {
-    f4 v = part[e];
-    for (int s = 1; s < nsplit; ++s) v += part[(int64_t)s * n4 + e];
-    out[e] = v;
-  }
-  if (outb != nullptr)
-    for (int64_t m = tid; m < M; m += stride) {
-      float v = partb[m];
-      for (int s = 1; s < nsplit; ++s) v += partb[(int64_t)s * M + m];
-      outb[m] = v;
-    }
-}
-
-constexpr int64_t kOffMax = (int64_t)1 << 31;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool is_half(int32_t dtype) { return dtype == MRP_DTYPE_BF16 || dtype == MRP_DTYPE_F16; }
 bool native_on() { return mrp_host::tuning().compress_half_cl != 0; }
 
 // a pixel-major operand of C channels: non-null, 16-byte aligned, strides whole 16-byte pieces,
@@ -420,23 +347,7 @@ hipError_t launch(int32_t dtype, Args a, hipStream_t st) {
   const int64_t grid = (int64_t)a.mtiles * ((a.nrows + TN - 1) / TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   a.group = mrp_host::tuning().gemm_group;
-  if (dtype == MRP_DTYPE_BF16)
-    hipLaunchKernelGGL(gemm_cl_half<BF16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(gemm_cl_half<F16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-// splits of K = nodes P in whole 32-row stages (the last one ragged): compress_split.hip's planner on the
-// stage count, or the count the "half_cl_splits" knob forces (clamped so that no split is empty)
-int plan_splits(int64_t M, int64_t N, int64_t ktot, int64_t* kchunk) {
-  const int64_t tiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-  const int64_t stages = (ktot + BK - 1) / BK;
-  const int forced = mrp_host::tuning().half_cl_splits;
-  if (forced <= 0) return mrp_cs::nt_splits(tiles, stages * BK, M, N, kchunk);
-  const int64_t per = (stages + forced - 1) / forced;
-  *kchunk = per * BK;
-  return (int)((stages + per - 1) / per);
+  return launch_t(dtype, gemm_cl_half<BF16>, gemm_cl_half<F16>, dim3((unsigned)grid), dim3(THREADS), st, a);
 }
 
 }  // namespace mrp_ccl
@@ -509,8 +420,8 @@ extern "C" int64_t mrp_compress_bwd_weight_cl_workspace(int32_t num_nodes, int32
   if (num_nodes <= 0 || C <= 0 || P <= 0 || C % 32 != 0) return 0;
   const int64_t M = C, N = 2 * (int64_t)C;
   int64_t kchunk;
-  const int ns = plan_splits(M, N, (int64_t)num_nodes * P, &kchunk);
-  return ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
+  const int ns = plan_splits(M, N, (int64_t)num_nodes * P, mrp_host::tuning().half_cl_splits, &kchunk);
+  return splitk_place(ns, M, N).bytes;
 }
 
 extern "C" int mrp_compress_bwd_weight_cl(int32_t dtype, const void* gy, int64_t gy_node_stride,
@@ -543,29 +454,7 @@ extern "C" int mrp_compress_bwd_weight_cl(int32_t dtype, const void* gy, int64_t
   a.s1p = agg_pixel_stride;
   a.n0 = C;
   a.P = P;
-  a.M = (int32_t)M;
-  a.N = (int32_t)N;
-  a.mtiles = (int32_t)((M + TM - 1) / TM);
-  a.ntiles = (int32_t)((N + TN - 1) / TN);
   a.ktot = (int64_t)num_nodes * P;
-  const int ns = plan_splits(M, N, a.ktot, &a.kchunk);
-  const int64_t need = ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need || !aligned16(workspace))) return hipErrorInvalidValue;
-  float* ws = static_cast<float*>(workspace);
-  a.out = ns <= 1 ? gw : ws;
-  a.outb = gbias == nullptr ? nullptr : (ns <= 1 ? gbias : ws + (int64_t)ns * M * N);
-  const int64_t grid = (int64_t)a.mtiles * a.ntiles * ns;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  a.group = mrp_host::tuning().nt_group;
-  if (dtype == MRP_DTYPE_BF16)
-    hipLaunchKernelGGL(gemm_wg_cl_half<BF16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(gemm_wg_cl_half<F16>, dim3((unsigned)grid), dim3(THREADS), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || ns <= 1) return e;
-  const int64_t n4 = M * N / 4;
-  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-  hipLaunchKernelGGL(split_sum_cl, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(ws), ns, n4,
-                     reinterpret_cast<f4*>(gw), a.outb, (int32_t)M, gbias);
-  return hipGetLastError();
+  return run_wgrad(dtype, gemm_wg_cl_half<BF16>, gemm_wg_cl_half<F16>, a, mrp_host::tuning().half_cl_splits, M, N, gw,
+                   gbias, workspace, workspace_bytes, st);
 }

@@ -45,19 +45,14 @@
 #include <mutex>
 #include <vector>
 
+#include "gemm_common.hpp"
 #include "mrp_gnn.h"
 #include "tuning.hpp"
 
 namespace mrp_cs {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+// vector types, rsrc, xcd_remap, tile_of, the LDS image offsets boff / rowoff: gemm_common.hpp
+using namespace mrp_gemm;
 
 constexpr int TN = 128, BK = 32;
 constexpr int B_PART_BYTES = BK * TN * 2;  // one bf16 part of the B stage: 8 KiB
@@ -164,11 +159,6 @@ __device__ __forceinline__ void pin(u4 (&r)[NP]) {
   for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(r[p]));
 }
 
-// byte offset of 16-byte chunk ch (8 columns) of row `row` in a [BK][TN] bf16 image
-__device__ __forceinline__ uint32_t boff(int row, int ch) {
-  return (uint32_t)(256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))));
-}
-
 // A (M x K) = w (row-major, M x K, stride lda) or w^T (w: K x M row-major, stride lda) -> packed parts
 __global__ void __launch_bounds__(256) pack(const float* __restrict__ w, int64_t lda, int trans, int M, int K,
                                             u4* __restrict__ out) {
@@ -213,26 +203,6 @@ struct Args {
   int32_t group;  // tile order (tile_of)
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-
-// Tile t of an mtiles x ntiles grid, in runs of `group` m-tiles walked m fastest (group <= 0: all of
-// them, round 4's order).  An XCD runs ~32 consecutive tiles at once (the XCD-aware remap gives it a
-// contiguous range), and they share its L2: with group 4 that window is 4 m-tiles x 8 column tiles,
-// so the L2 misses per window are 4 row blocks of the packed operand plus 8 column blocks of the
-// streamed one — at configs[3] (8 m-tiles x 32 column tiles) 42 MB per XCD against 59 MB for 8 x 4,
-// and for its data gradient (16 m-tiles) 21 against 52 MB.
-__device__ __forceinline__ void tile_of(int t, int mtiles, int ntiles, int group, int& mt, int& nt) {
-  const int gmax = group > 0 && group < mtiles ? group : mtiles;
-  const int run = gmax * ntiles;
-  const int g = t / run, first = g * gmax;
-  const int gm = mtiles - first < gmax ? mtiles - first : gmax;
-  const int rem = t - g * run;
-  mt = first + rem % gm;
-  nt = rem / gm;
-}
-
 template <int WMW, bool MF16 = false, int NP = 3>
 __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
   using G = Geo<WMW, NP>;
@@ -241,9 +211,8 @@ __device__ __forceinline__ void gemm_nn_split_body(const Args& a) {
   char* ldsb = reinterpret_cast<char*>(lds);
   // XCD-aware tile order: the m tiles of one column tile run on one XCD and share its L2 (B is read
   // once from HBM per column tile)
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+  const int nwg = gridDim.x;
+  const int id = xcd_remap(blockIdx.x, nwg);
   int mt, nt;
   tile_of(id, a.mtiles, nwg / a.mtiles, a.group, mt, nt);
   const int64_t nbase = (int64_t)nt * TN;
@@ -556,10 +525,6 @@ __global__ void __launch_bounds__(512, 1) gemm_nn_split_w4_mf16(Args a) {
   gemm_nn_split_body<4, true, NP>(a);
 }
 
-constexpr int64_t kOffMax = (int64_t)1 << 31;
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
 template <int WMW, int NP, void (*K)(Args)>
 hipError_t launch_w(Args a, hipStream_t st) {
@@ -642,11 +607,6 @@ struct NTGeo {
   static constexpr int AJ = TM / RPP, BJ = TN / RPP;                   // A / B pieces per thread per stage
 };
 
-__device__ __forceinline__ uint32_t rowoff(int row, int chunk) {  // [row][4 chunks of 16 B], rotated
-  return (uint32_t)(64 * row + 16 * (chunk ^ ((row >> 2) & 3)));
-}
-
-
 // The products on v_mfma_f32_16x16x32_bf16 (the wave's 64 x 64 as 4 x 4 tiles of 16 x 16, one MFMA per
 // 32 k), which holds a higher clock than the 32x32x16 shape under the chip's power limit
 // (MI355X_MICROARCH.md, DVFS give-back item 7); the 32x32x16 forms are lab forms (tools/lab_forms.hip)
@@ -655,8 +615,7 @@ __device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, in
   using G = NTGeo<WMW, NP>;
   extern __shared__ u4 lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + orig / 8;
+  const int id = xcd_remap(orig, nwg);
   const int tiles = a.mtiles * a.ntiles;
   const int split = id / tiles, tid = id - split * tiles;
   int mt, nt;
@@ -889,8 +848,7 @@ static __device__ __forceinline__ void run(const NTArgs& a, int orig, int nwg) {
   constexpr int BP = G::B_PART, BUF = A_BYTES + NP * BP;  // NP 3: 72 KiB per buffer, two buffers
   extern __shared__ u4 lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
-  const int q8 = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + orig / 8;
+  const int id = xcd_remap(orig, nwg);
   const int tiles = a.mtiles * a.ntiles;
   const int split = id / tiles, tid = id - split * tiles;
   int mt, nt;
@@ -1121,10 +1079,21 @@ __global__ void __launch_bounds__(256) split_sum_nt(const f4* __restrict__ part,
     }
 }
 
+}  // namespace mrp_cs
+
+hipError_t mrp_gemm::split_sum(const float* part, int nsplit, int64_t M, int64_t N, float* out, const float* partb,
+                               int nsplitb, float* outb, hipStream_t st) {
+  const int64_t n4 = M * N / 4;
+  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
+  hipLaunchKernelGGL(mrp_cs::split_sum_nt, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(part),
+                     nsplit, n4, reinterpret_cast<f4*>(out), partb, nsplitb, (int32_t)M, outb);
+  return hipGetLastError();
+}
+
 // Splits of K = Nt P (whole stages): the count minimising (rounds of one-per-CU workgroups) x
 // (stages per split) plus the partial-tile traffic of the final sum.
-int nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk) {
-  const int64_t stages = ktot / BK;
+int mrp_gemm::nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk) {
+  const int64_t stages = ktot / mrp_cs::BK;
   int best = 1;
   double best_cost = 1e300;
   for (int s = 1; s <= 256; ++s) {
@@ -1139,11 +1108,9 @@ int nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk
       best = s;
     }
   }
-  *kchunk = ((stages + best - 1) / best) * BK;
+  *kchunk = ((stages + best - 1) / best) * mrp_cs::BK;
   return best;
 }
-
-}  // namespace mrp_cs
 
 using namespace mrp_cs;
 
@@ -1251,8 +1218,7 @@ bool nt_split_ok(int32_t num_nodes, int32_t C, int32_t P) {
 int64_t nt_workspace(int64_t M, int64_t N, int64_t ktot) {
   const int64_t tiles = ((M + NTGeo<4>::TM - 1) / NTGeo<4>::TM) * ((N + TN - 1) / TN);
   int64_t kchunk;
-  const int ns = nt_splits(tiles, ktot, M, N, &kchunk);
-  return ns <= 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
+  return splitk_place(nt_splits(tiles, ktot, M, N, &kchunk), M, N).bytes;
 }
 
 // one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
@@ -1285,11 +1251,10 @@ hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, flo
   a.ntiles = (int32_t)((N + TN - 1) / TN);
   a.ktot = (int64_t)nodes * a.P;
   const int ns = nt_splits((int64_t)a.mtiles * a.ntiles, a.ktot, M, N, &a.kchunk);
-  const int64_t need = ns == 1 ? 0 : ((int64_t)ns * M * N + (int64_t)ns * M) * 4;
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need || !aligned16(workspace))) return hipErrorInvalidValue;
-  float* ws = static_cast<float*>(workspace);
-  a.out = ns == 1 ? out : ws;
-  a.outb = outb == nullptr ? nullptr : (ns == 1 ? outb : ws + (int64_t)ns * M * N);
+  const SplitK pl = splitk_place(ns, M, N, out, outb, workspace, workspace_bytes);
+  if (pl.err != hipSuccess) return pl.err;
+  a.out = pl.out;
+  a.outb = pl.outb;
   a.M = (int32_t)M;
   a.N = (int32_t)N;
   const int64_t grid = (int64_t)a.mtiles * a.ntiles * ns;
@@ -1300,11 +1265,7 @@ hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, flo
   a.group = mrp_host::tuning().nt_group;
   hipError_t e = parts == 3 ? launch_nt<3>(a, grid, st) : parts == 2 ? launch_nt<2>(a, grid, st) : launch_nt<1>(a, grid, st);
   if (e != hipSuccess || ns == 1) return e;
-  const int64_t n4 = M * N / 4;
-  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-  hipLaunchKernelGGL(split_sum_nt, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(ws), ns, n4,
-                     reinterpret_cast<f4*>(out), a.outb, ns, (int32_t)M, outb);
-  return hipGetLastError();
+  return split_sum(pl.out, ns, M, N, out, pl.outb, ns, outb, st);
 }
 
 // The pre-split-A weight gradient (split_rows + gemm_nt_psa): workspace = [partial tiles (splits > 1)]
@@ -1367,11 +1328,7 @@ hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* 
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (q.ns == 1) return hipSuccess;
-  const int64_t n4 = M * N / 4;
-  const int64_t blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
-  hipLaunchKernelGGL(split_sum_nt, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const f4*>(tiles_ws), q.ns,
-                     n4, reinterpret_cast<f4*>(out), nullptr, 0, (int32_t)M, nullptr);
-  return hipGetLastError();
+  return split_sum(static_cast<const float*>(tiles_ws), q.ns, M, N, out, nullptr, 0, nullptr, st);
 }
 
 // (the plan, and so the workspace layout and bound, is the same for every part count: a reduced form's

@@ -102,9 +102,7 @@ __device__ __forceinline__ void encoder2_body(const FwdArgs& a) {
   const int eblocks = (a.E + 31) / 32;
   // workgroup -> (column group, edge block); consecutive ids share a column group (its W2 slab) and,
   // after the remap, an XCD and its L2
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + orig / 8;
+  const int id = mrp_gemm::xcd_remap(blockIdx.x, gridDim.x);
   const int eb = id % eblocks, cg = id / eblocks;
   const int ngroups = (ncb + CPG - 1) / CPG;
   const int lane = threadIdx.x & 63;

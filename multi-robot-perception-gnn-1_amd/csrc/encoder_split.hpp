@@ -9,16 +9,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_common.hpp"
+
 namespace mrp_x6 {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+using mrp_gemm::bf2;
+using mrp_gemm::bf8;
+using mrp_gemm::f16v;
+using mrp_gemm::f2;
+using mrp_gemm::u4;
 
 constexpr int kNin = 9;
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 
 // two fp32 -> two bf16 (round to nearest even) in one dword: v_cvt_pk_bf16_f32
 __device__ __forceinline__ uint32_t cvt2(f2 x) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf2)); }

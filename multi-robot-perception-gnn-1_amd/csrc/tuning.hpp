@@ -47,7 +47,7 @@ struct Tuning {
   // offsets, else (and for the encoder's products) 3 (the default below C = 1024): the 32-k-stage form
   // on 16x16x32 MFMAs splitting both operands
   int split_nt = -1;
-  // split-bf16 GEMMs' tile order (compress_split.hip tile_of): runs of this many 256-row tiles, m
+  // split-bf16 GEMMs' tile order (gemm_common.hpp tile_of): runs of this many 256-row tiles, m
   // fastest (0: all, round 4's order).  Forward / data gradient 4 (configs[3] 1.4-1.8 % faster, the
   // others flat; tools/ab_gemm.py knob:gemm_group=0,4); weight gradient 0 (4 measured 1.6-2.7 % slower
   // at configs[2] and [3])
@@ -58,7 +58,7 @@ struct Tuning {
   int enc_bwd_psa = 2;
   int enc_s1 = 0, enc_s2 = 0;  // mrp_edge_encoder_bwd_fused: split counts of its two products (0: planner)
   // the bf16 / fp16 compress (compress_half.hip): 0 = its entry points decline every shape (A/B runs);
-  // the weight gradient's split-K count (0: compress_split.hip's planner)
+  // the weight gradient's split-K count (0: the planner, gemm_common.hpp nt_splits)
   int compress_half = 1;
   int half_nt_splits = 0;
   // the pixel-major bf16 / fp16 compress (compress_half_cl.hip): the same two knobs for its entry points

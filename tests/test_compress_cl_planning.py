@@ -21,7 +21,7 @@ BK, TN = 32, 128
 
 
 def forced_plan(ktot, forced):
-    """compress_half_cl.hip plan_splits, forced > 0: (number of splits, rows per split)."""
+    """compress_half_common.hpp plan_splits, forced > 0: (number of splits, rows per split)."""
     stages = (ktot + BK - 1) // BK
     per = (stages + forced - 1) // forced
     return (stages + per - 1) // per, per * BK

@@ -1,7 +1,7 @@
 """Profiling driver (not product code): a few GCN-stack training steps (forward + backward + every
 parameter gradient) and no-grad forwards of every BASELINE config, so one
 ``rocprofv3 --kernel-trace --stats`` pass shows which kernels a step launches (the compress must be
-``gemm_nn``/``gemm_nt``/``split_sum``, no ``Cijk_*``/MIOpen).
+``gemm_nn``/``gemm_nt``/``split_sum_nt``, no ``Cijk_*``/MIOpen).
 Usage: python tools/prof_train_step.py [steps] [config ids, default all] [--no-fwd]"""
 import os
 import sys

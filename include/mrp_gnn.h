@@ -555,6 +555,55 @@ int mrp_compress_bwd_weight_cl(int32_t dtype, const void* gy, int64_t gy_node_st
                                void* stream);
 
 /*
+ * The split-bf16 compress on pixel-major (torch.channels_last) fp32 feature maps (compress_split_cl.hip):
+ * the _split_p entry points' three products with every feature tensor a (pointer, node stride, pixel
+ * stride) triple in elements, as the _cl entry points above define it (pixel stride C for a dense
+ * channels_last map, 2C for either half of a channels_last concatenation buffer; node_stride >=
+ * P * pixel_stride).  The arithmetic is the _split_p block's: the exact bf16 split of each fp32 operand,
+ * the partial products with i + j < parts (parts = 3: fp32 accuracy; 2 / 1: the reduced forms and their
+ * per-term bounds stated there), a0 b0 in an accumulator of its own, fp32 accumulation and outputs; the
+ * k order inside a product differs from the node-major kernels', so results agree with them to fp32
+ * rounding, not bit for bit.  The packed weight images are mrp_compress_split_pack's, the same for
+ * every `parts`: pack(w, 2C, 0, C, 2C) for the forward, pack(w, 2C, 1, 2C, C) for the data gradient.
+ *   mrp_compress_fwd_split_cl            y = W [x; agg] + bias (C, may be NULL) per pixel row
+ *   mrp_compress_bwd_data_split_cl       [gx; gagg] = W^T gy: two pixel-major outputs with their own
+ *                                        strides (e.g. the halves of one channels_last 2C buffer)
+ *   mrp_compress_bwd_weight_split_cl     gw (C, 2C) = sum gy [x; agg]^T and gbias (C, may be NULL) = sum gy
+ *                                        over all num_nodes P pixel rows; K = num_nodes P is split over
+ *                                        workgroups into fp32 partial tiles in workspace
+ *                                        (mrp_compress_bwd_weight_split_cl_workspace bytes, 16-byte
+ *                                        aligned; 0: none needed; the bound holds for every `parts`)
+ *                                        summed in a fixed order by a second launch: no atomics, two runs
+ *                                        give the same bits.  gbias is the fp32 sum of the full gy for
+ *                                        every `parts`.
+ * Pixels are rows: any P is tiled (no padding; a tile or stage may cross a node boundary).  Operands and
+ * outputs are addressed through 64-bit arithmetic: no span limit, no per-node-range calls.  Returns, all
+ * before any launch: `parts` outside {1, 2, 3}: hipErrorInvalidValue before anything else; a NULL pointer
+ * with work to do, a pointer that is not 16-byte aligned, a node or pixel stride that is not a multiple of
+ * 4 elements, a pixel stride below C, a node stride below P pixel strides, a workspace that is too small
+ * or gw == NULL with gbias != NULL: hipErrorInvalidValue; zero sizes: success without a launch (an empty
+ * weight-gradient sum zeroes gw / gbias; gw and gbias both NULL is a no-op); C % 32 != 0, a pixel-row
+ * count or a packed image beyond 31 bits — and every shape while the tuning knob "compress_split_cl" is
+ * 0 — hipErrorNotSupported.  The knob "split_cl_splits" forces the weight gradient's split-K count
+ * (0 default = the planner's).  The error model otherwise is the _split_p block's.  No host
+ * synchronisation; stream-capturable.
+ */
+int mrp_compress_fwd_split_cl(const float* x, int64_t x_node_stride, int64_t x_pixel_stride, const float* agg,
+                              int64_t agg_node_stride, int64_t agg_pixel_stride, int32_t num_nodes, int32_t C,
+                              int32_t P, const void* packed_w, const float* bias, float* y, int64_t y_node_stride,
+                              int64_t y_pixel_stride, int32_t parts, void* stream);
+int mrp_compress_bwd_data_split_cl(const float* gy, int64_t gy_node_stride, int64_t gy_pixel_stride,
+                                   int32_t num_nodes, int32_t C, int32_t P, const void* packed_wt, float* gx,
+                                   int64_t gx_node_stride, int64_t gx_pixel_stride, float* gagg,
+                                   int64_t gagg_node_stride, int64_t gagg_pixel_stride, int32_t parts, void* stream);
+int64_t mrp_compress_bwd_weight_split_cl_workspace(int32_t num_nodes, int32_t C, int32_t P);
+int mrp_compress_bwd_weight_split_cl(const float* gy, int64_t gy_node_stride, int64_t gy_pixel_stride, const float* x,
+                                     int64_t x_node_stride, int64_t x_pixel_stride, const float* agg,
+                                     int64_t agg_node_stride, int64_t agg_pixel_stride, int32_t num_nodes, int32_t C,
+                                     int32_t P, float* gw, float* gbias, void* workspace, int64_t workspace_bytes,
+                                     int32_t parts, void* stream);
+
+/*
  * First layer of the edge encoder, dgl/model/models.py:147-148:  h = relu(pose W1^T + b1).
  *   pose (num_edges, 9), w1 (C, 9) (nn.Linear weight layout), b1 (C) -> h (num_edges, C), fp32.
  * The second Linear is mrp_edge_logits_fwd and its Sigmoid is fused into the aggregation
@@ -718,7 +767,9 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * "half_nt_splits" (mrp_compress_bwd_weight_t's split-K count, 0 default = the planner's, 1..256);
  * "compress_half_cl" (1 default; 0 = the pixel-major compress entry points mrp_compress_*_cl decline
  * every shape, for A/B runs); "half_cl_splits" (mrp_compress_bwd_weight_cl's split-K count, 0 default =
- * the planner's, 1..256). */
+ * the planner's, 1..256); "compress_split_cl" (1 default; 0 = the pixel-major fp32 entry points
+ * mrp_compress_*_split_cl decline every shape) and "split_cl_splits"
+ * (mrp_compress_bwd_weight_split_cl's split-K count, 0 default = the planner's, 1..256). */
 int mrp_tuning_set(const char* name, int32_t value);
 
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
@@ -728,7 +779,9 @@ int mrp_tuning_set(const char* name, int32_t value);
  * _bwd_weight_t_workspace / _bwd_weight_t and the knobs "compress_half" / "half_nt_splits", and their
  * pixel-major forms mrp_compress_fwd_cl / _bwd_data_cl / _bwd_weight_cl_workspace / _bwd_weight_cl with the
  * knobs "compress_half_cl" / "half_cl_splits", and the part-count forms of the split-bf16 compress
- * mrp_compress_fwd_split_p / _bwd_data_split_p / _bwd_weight_split_p; 21: v19 plus
+ * mrp_compress_fwd_split_p / _bwd_data_split_p / _bwd_weight_split_p, and their pixel-major fp32 forms
+ * mrp_compress_fwd_split_cl / _bwd_data_split_cl / _bwd_weight_split_cl_workspace / _bwd_weight_split_cl
+ * with the knobs "compress_split_cl" / "split_cl_splits"; 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

@@ -12,6 +12,7 @@ from .aggregate import (EpilogueSpec, FilmMeanFunction, film_mean, film_mean_cat
                         pixel_strides, set_channels_last)
 from . import compat, compress, encoder  # noqa: F401
 from .compress import compress_precision, compress_precision_scope, set_compress_precision  # noqa: F401
+from .compress import channels_last_compress_fp32, set_channels_last_compress_fp32  # noqa: F401
 from .device_graph import frame_batch  # noqa: F401
 from .graph import (GraphCSR, RobotGraph, batch, complete_edges, complete_graph, frame_graph,  # noqa: F401
                     graph, knn_edges, load_graphs, save_graphs, unbatch)

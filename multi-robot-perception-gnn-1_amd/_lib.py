@@ -54,6 +54,10 @@ EXPORTED_SYMBOLS = (
     "mrp_compress_bwd_data_cl",
     "mrp_compress_bwd_weight_cl_workspace",
     "mrp_compress_bwd_weight_cl",
+    "mrp_compress_fwd_split_cl",
+    "mrp_compress_bwd_data_split_cl",
+    "mrp_compress_bwd_weight_split_cl_workspace",
+    "mrp_compress_bwd_weight_split_cl",
     "mrp_edge_hidden_fwd",
     "mrp_edge_logits_fwd",
     "mrp_edge_encoder_pack_bytes",
@@ -204,6 +208,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_compress_bwd_weight_cl_workspace.restype = ctypes.c_int64
     lib.mrp_compress_bwd_weight_cl.argtypes = [_I32] + t3 + t3 + t3 + [_I32, _I32, _I32, _P, _P, _P, _I64, _P]
     lib.mrp_compress_bwd_weight_cl.restype = ctypes.c_int
+    # the pixel-major fp32 forms: no dtype, `parts` before the stream
+    lib.mrp_compress_fwd_split_cl.argtypes = lib.mrp_compress_fwd_cl.argtypes[1:-1] + [_I32, _P]
+    lib.mrp_compress_fwd_split_cl.restype = ctypes.c_int
+    lib.mrp_compress_bwd_data_split_cl.argtypes = lib.mrp_compress_bwd_data_cl.argtypes[1:-1] + [_I32, _P]
+    lib.mrp_compress_bwd_data_split_cl.restype = ctypes.c_int
+    lib.mrp_compress_bwd_weight_split_cl_workspace.argtypes = [_I32, _I32, _I32]
+    lib.mrp_compress_bwd_weight_split_cl_workspace.restype = ctypes.c_int64
+    lib.mrp_compress_bwd_weight_split_cl.argtypes = lib.mrp_compress_bwd_weight_cl.argtypes[1:-1] + [_I32, _P]
+    lib.mrp_compress_bwd_weight_split_cl.restype = ctypes.c_int
     lib.mrp_edge_hidden_fwd.argtypes = [_P, _P, _P, _I32, _I32, _P, _P]
     lib.mrp_edge_hidden_fwd.restype = ctypes.c_int
     lib.mrp_edge_logits_fwd.argtypes = [_P, _I32, _I32, _P, _P, _P, _P]

@@ -3,6 +3,7 @@
 // xcd_remap, tile_of, the LDS image offsets boff / rowoff, the split-K host helpers): the MFMA per type,
 // the workgroup's tile and stage sizes, the weight-operand side of the forward / data-gradient kernels,
 // the weight-gradient kernels' partial-tile store and the host tail of the two weight gradients.
+// (plan_splits also plans the pixel-major fp32 weight gradient of compress_split_cl.hip: same tile, same stage.)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -70,6 +70,8 @@ int mrp_tuning_set(const char* name, int32_t value) {
       {"half_nt_splits", &t.half_nt_splits, 0, 256},
       {"compress_half_cl", &t.compress_half_cl, 0, 1},
       {"half_cl_splits", &t.half_cl_splits, 0, 256},
+      {"compress_split_cl", &t.compress_split_cl, 0, 1},
+      {"split_cl_splits", &t.split_cl_splits, 0, 256},
   };
   for (const Knob& k : knobs) {
     if (std::strcmp(name, k.name) == 0) {

@@ -1,5 +1,6 @@
 // gemm_common.hpp — what more than one of the GEMM translation units (compress_gemm.hip,
-// compress_split.hip, compress_half.hip, compress_half_cl.hip, encoder_split.hip) uses: vector types,
+// compress_split.hip, compress_split_cl.hip, compress_half.hip, compress_half_cl.hip, encoder_split.hip)
+// uses: vector types,
 // the buffer resource, the workgroup -> tile order, the 16-bit LDS image layouts, and the host side of
 // the split-K weight gradients (planner, workspace placement, the sum of the partial tiles).
 #pragma once

@@ -64,6 +64,9 @@ struct Tuning {
   // the pixel-major bf16 / fp16 compress (compress_half_cl.hip): the same two knobs for its entry points
   int compress_half_cl = 1;
   int half_cl_splits = 0;
+  // the pixel-major fp32 split-bf16 compress (compress_split_cl.hip): the same two knobs for its entry points
+  int compress_split_cl = 1;
+  int split_cl_splits = 0;
 };
 Tuning& tuning();
 

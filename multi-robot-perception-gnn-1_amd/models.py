@@ -175,7 +175,9 @@ class GCN(_PackedImages, nn.Module):
         then ``conv(h)`` by torch.  ``torch.channels_last`` bf16 / fp16 features (C % 32 == 0) stay
         channels_last through the layer and its backward: the pixel-major aggregation and compress
         kernels read and write them in place (``compress_half_cl.hip``;
-        ``compress.set_channels_last_compress('convert')`` restores the copy to NCHW)."""
+        ``compress.set_channels_last_compress('convert')`` restores the copy to NCHW); fp32 channels_last
+        features do the same after ``compress.set_channels_last_compress_fp32('native')``
+        (``compress_split_cl.hip``; by default they are copied to NCHW and the layer returns NCHW)."""
         x = feats
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):

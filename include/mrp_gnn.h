@@ -34,6 +34,27 @@
  *  - Return value: 0 on success, otherwise a hipError_t value
  *    (hipErrorInvalidValue = 1 for bad shapes/arguments).  No exceptions cross
  *    the ABI.  Stateless and re-entrant.
+ *  - Special values (tests/test_gpu_special_values.py).  A non-finite input stays visible — whatever the
+ *    reference operation makes non-finite is non-finite here — and stays confined:
+ *      aggregation forward: exactly the reference's set.  A non-neighbour, an edgeless node, a clamped
+ *        load of a ragged batch are skipped, never multiplied by zero; xcopy carries x's bits, a NaN's
+ *        payload included;
+ *      aggregation backward: see mrp_film_mean_bwd (the graph, channel and pixel of the poisoned element);
+ *      compress (all four families, every `parts`): a dense product — x or agg at (n, c, p) makes
+ *        y[n, :, p] non-finite, gy at (n, o, p) makes gx[n, :, p] and gagg[n, :, p] non-finite, and in the
+ *        weight gradient column c of gw (x, agg) or row o of gw and gbias[o] (gy); nothing else changes;
+ *      edge encoder: pose[e, j] makes every logit of row e (and h[e, :] / hT[:, e] where the reference's
+ *        is) non-finite — both ReLUs keep a NaN of either sign, as torch.relu does; no other row changes.
+ *    An infinity may come back as NaN from the split-bf16 kernels.  The mean's division is the IEEE
+ *    quotient for every sum: +0, subnormals, +-inf and NaN included (the fast division is used only for
+ *    groups of sums with 2^-124 <= |s| < inf).  The fused sigmoid (MRP_AGG_GB_LOGITS) saturates: within
+ *    (2.5 2^-23 + 2^-24 |z|) relative + 2^-126 absolute of the exact value for every z, exactly 1 from
+ *    z = 20 + 24 ln 2 on, exactly 0 at z = -inf (the absolute term is one flushed subnormal: 1 / e^-z below
+ *    about z = -87.3); its backward is exactly 0 at z = +-inf and |z| >= 104; a NaN logit stays in its own
+ *    (edge, channel).  Every store to bf16 / fp16 is one round to nearest even of the fp32 result:
+ *    overflow gives +-inf, results in T's subnormal range are kept, NaN stays NaN, -0 stays -0; bf16 / fp16
+ *    subnormal operands are kept by the matrix cores.  The domain of the split-bf16 kernels is stated at
+ *    mrp_compress_fwd_split.
  */
 #ifndef MRP_GNN_H
 #define MRP_GNN_H
@@ -140,6 +161,11 @@ int mrp_film_mean_cat_fwd(const float* x, int64_t x_node_stride,
  * torch.cat((x, out), 1) (dgl/model/models.py:182) passes the first half of the concatenation's
  * gradient here and the second half as grad_out, so x's total gradient is one pass.
  * Deterministic: no atomics; each output element is written by exactly one lane.
+ * Non-finite values: the transposed tiles are dense within a graph (a matrix-core kernel multiplies every
+ * node pair of it), so a non-finite grad_out[v, c, p] may make grad_x non-finite at (any node of v's graph,
+ * c, p) and grad_gb at (any edge of v's graph, c) — never outside them, and always wherever the formulas
+ * above do; a non-finite x[u, c, p] leaves grad_x's bits unchanged and is confined in grad_gb to (the edges
+ * of u's graph, c).  Some kernels are stricter ("Special values"); only this is promised.
  */
 int mrp_film_mean_bwd(const float* grad_out, int64_t g_node_stride,
                       const float* x, int64_t x_node_stride,
@@ -387,7 +413,14 @@ int mrp_compress_bwd_weight(const float* gy, int64_t gy_node_stride, const float
  * (compress_split.hip): the same products as mrp_compress_fwd / mrp_compress_bwd_data, each fp32
  * operand split exactly into three bf16 parts and each product the sum of the six partial products
  * whose omitted terms are below 2^-25 of it (error against float64 about an fp32 GEMM's: measured 0.3 to
- * 0.9 x torch's at K = 1024, bounded by 2 x in tests/test_gpu_split_fp32.py).  The
+ * 0.9 x torch's at K = 1024, bounded by 2 x in tests/test_gpu_split_fp32.py).
+ * Domain (every split-bf16 kernel: compress, node-major and pixel-major, and the edge encoder): the accuracy
+ * is relative to sum |a_k b_k| and independent of the operands' scale — scaling the operands by powers of two
+ * scales the result bit for bit — as long as every non-zero bf16 part of every operand is a normal bf16 and
+ * nothing overflows (tested for operands scaled by 2^-100 .. 2^100, products by 2^-110 .. 2^120); below
+ * that the low parts are lost and the accuracy degrades towards bf16's.  A finite operand with
+ * |x| >= 2^128 - 2^119 (0x7f7f8000) is outside the domain: it rounds to a bf16 infinity, its residual is
+ * -inf, and every product that reads it is NaN (its output row or column; nothing else).  The
  * weight operand is split and laid out once per weight version:
  *   mrp_compress_split_pack_bytes(M, K)   bytes of a packed M x K operand (0 unless M % 32 == 0, K % 16 == 0)
  *   mrp_compress_split_pack(w, ld, transpose, M, K, packed)

@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) edge_hidden_fwd(const float* __restrict__
       float acc = w[j][NIN];
 #pragma unroll
       for (int i = 0; i < NIN; ++i) acc = fmaf(p[i], w[j][i], acc);
-      h[(int64_t)e * C + k] = acc > 0.f ? acc : 0.f;
+      h[(int64_t)e * C + k] = acc < 0.f ? 0.f : acc;  // keeps NaN, as torch.relu (acc > 0 ? acc : 0 drops it)
     }
   }
 }

@@ -52,8 +52,9 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf8 (&p)[3]) {
   p[2] = __builtin_bit_cast(bf8, c);
 }
 
-// max(x, 0) on the bit pattern (negative floats, -0 included, are negative integers): one v_max_i32
-__device__ __forceinline__ float relu(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
+// relu that keeps a NaN of either sign, as torch.relu does (a compare and a select; an integer max on the
+// bit pattern turns a NaN with its sign bit set into 0, fmaxf(x, 0) every NaN)
+__device__ __forceinline__ float relu(float x) { return x < 0.f ? 0.f : x; }
 
 __device__ __forceinline__ bf8 as_bf8(u4 v) { return __builtin_bit_cast(bf8, v); }
 __device__ __forceinline__ u4 as_u4(bf8 v) { return __builtin_bit_cast(u4, v); }

@@ -775,7 +775,10 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
 /* Experiment knobs of the launchers (kernel-lab sweeps; not needed for normal use; process-wide,
  * not thread-safe).  Returns hipErrorInvalidValue for an unknown name or a value out of range;
  * "reset" restores every default.  Geometry: "fwd_lo"/"fwd_hi"/"fwd_cap", "fwd_regular_*",
- * "bwd_fused_*", "bwd_regular_*"; kernel choice: "bwd_regular_mfma" (1, default: the matrix-core
+ * "bwd_fused_*", "bwd_regular_*" (the planners clamp what a kernel cannot run: at most 64 lanes per plane
+ * in film_bwd_regular, channels per workgroup halved until the dynamic LDS fits 64 KiB; see
+ * mrp_film_mean_fwd_plan below, which reports the geometry a setting gives); kernel choice:
+ * "bwd_regular_mfma" (1, default: the matrix-core
  * backward for MRP_GRAPH_REGULAR graphs of 9..16 nodes), "bwd_complete_mfma" (1, default: the
  * matrix-core backward for complete graphs of 9..16 nodes too; those of <= 8 always run the VALU
  * one), "bwd_half_mfma" (1, default: 16-bit features run the matrix-core backward wherever the two
@@ -805,6 +808,76 @@ int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int
  * (mrp_compress_bwd_weight_split_cl's split-K count, 0 default = the planner's, 1..256). */
 int mrp_tuning_set(const char* name, int32_t value);
 
+/*
+ * The launch plan of the aggregation: what mrp_film_mean_fwd_t / mrp_film_mean_bwd_t would launch for
+ * these arguments under the current knobs, computed by the very function the launch path calls and
+ * without any GPU call (it works on a machine with no GPU).  tests/test_geometry_cpu.py walks the
+ * geometry knobs over their accepted ranges through it and tools/sweep_geometry.py prints it beside
+ * every timing.
+ *
+ * What the planners do beyond the knobs' values (so no accepted setting reaches a kernel outside its
+ * requirements):
+ *   - lanes per plane are a power of two <= P / vec; channels per workgroup fill at most 256 threads;
+ *   - film_bwd_regular reduces a plane's partial sums over one wave: "bwd_regular_lanes" gives at most
+ *     64 lanes per plane (1-element slices ask for twice the knob, capped at 64);
+ *   - no launcher raises the 64 KiB limit of dynamic LDS: the channels per workgroup are halved until the
+ *     kernel's request fits ("bwd_fused_cap" = 64 with logits on planes of 4 slices, and the Gram pass of
+ *     complete 16-node graphs with logits at 16 channels, run 32 and 8 channels).  film_bwd_dx, launched
+ *     before that Gram pass with the same geometry, runs the 8 channels with it (alone, when no gamma/beta
+ *     gradient is wanted, it keeps its 16).
+ */
+enum mrp_agg_kernel {
+  MRP_AGG_KERNEL_NONE = 0,             /* nothing to launch (empty sizes, no gradient wanted) */
+  MRP_AGG_KERNEL_FILM_FWD = 1,         /* film_fwd */
+  MRP_AGG_KERNEL_FILM_FWD_REGULAR = 2, /* film_fwd_regular (MRP_GRAPH_REGULAR(k), k <= 8) */
+  MRP_AGG_KERNEL_FILM_BWD_FUSED = 3,   /* film_bwd_fused, one pass (graphs of <= 8 nodes) */
+  MRP_AGG_KERNEL_FILM_BWD_DX_GRAM = 4, /* film_bwd_dx, then film_bwd_fused's 4-row Gram pass (> 8 nodes) */
+  MRP_AGG_KERNEL_FILM_BWD_REGULAR = 5, /* film_bwd_regular (fp32, > 8 nodes, MRP_GRAPH_REGULAR(k), k <= 8) */
+  MRP_AGG_KERNEL_FILM_BWD_MFMA = 6     /* film_bwd_mfma (9..16 nodes, P % 64 == 0, 4-element slices) */
+};
+
+typedef struct mrp_agg_plan {
+  int32_t kernel;    /* enum mrp_agg_kernel */
+  int32_t vec;       /* slice width in elements */
+  int32_t lpc;       /* lanes per channel plane */
+  int32_t cpb;       /* channels per workgroup */
+  int32_t threads;   /* workgroup size = cpb * lpc (film_bwd_mfma: 256) */
+  int32_t psplit;    /* forward: workgroups a plane is cut over (backward: 1) */
+  int32_t ncb;       /* channel blocks per graph */
+  int32_t pre2;      /* film_bwd_fused: the instantiation that prefetches both of a lane's two slices */
+  int64_t grid;      /* workgroups = num_graphs * ncb * psplit */
+  int64_t lds_bytes; /* dynamic LDS (MRP_AGG_KERNEL_FILM_BWD_DX_GRAM: the larger of its launches') */
+} mrp_agg_plan;
+
+/* The arguments of mrp_film_mean_fwd_t / mrp_film_mean_bwd_t without the stream.  Device pointers are
+ * used for their alignment and for being NULL only, never dereferenced (`epilogue` is host memory and is
+ * read).  Returns what the launch entry point would return before launching, with *plan filled on
+ * success (kernel = MRP_AGG_KERNEL_NONE where the entry point returns success without a launch); a NULL
+ * plan returns hipErrorInvalidValue. */
+int mrp_film_mean_fwd_plan(int32_t dtype,
+                           const void* x, int64_t x_node_stride,
+                           const float* gb,
+                           const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                           const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                           int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                           int32_t C, int32_t P, int32_t mode,
+                           void* out, int64_t out_node_stride,
+                           const mrp_agg_epilogue* epilogue,
+                           mrp_agg_plan* plan);
+int mrp_film_mean_bwd_plan(int32_t dtype,
+                           const void* grad_out, int64_t g_node_stride,
+                           const void* x, int64_t x_node_stride,
+                           const float* gb,
+                           const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                           const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                           int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                           int32_t C, int32_t P, int32_t mode,
+                           void* grad_x, int64_t gx_node_stride,
+                           const void* grad_x_base, int64_t base_node_stride,
+                           float* grad_gb,
+                           const mrp_agg_epilogue* epilogue,
+                           mrp_agg_plan* plan);
+
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
  * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature
  * tensors, enum mrp_dtype) and, added since without a new number (nothing existing changed), the
@@ -814,7 +887,8 @@ int mrp_tuning_set(const char* name, int32_t value);
  * knobs "compress_half_cl" / "half_cl_splits", and the part-count forms of the split-bf16 compress
  * mrp_compress_fwd_split_p / _bwd_data_split_p / _bwd_weight_split_p, and their pixel-major fp32 forms
  * mrp_compress_fwd_split_cl / _bwd_data_split_cl / _bwd_weight_split_cl_workspace / _bwd_weight_split_cl
- * with the knobs "compress_split_cl" / "split_cl_splits"; 21: v19 plus
+ * with the knobs "compress_split_cl" / "split_cl_splits", and the host-only plan queries
+ * mrp_film_mean_fwd_plan / mrp_film_mean_bwd_plan (enum mrp_agg_kernel, mrp_agg_plan); 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

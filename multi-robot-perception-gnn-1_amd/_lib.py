@@ -26,6 +26,8 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_bwd_ex",
     "mrp_film_mean_fwd_t",
     "mrp_film_mean_bwd_t",
+    "mrp_film_mean_fwd_plan",
+    "mrp_film_mean_bwd_plan",
     "mrp_film_mean_bwd_workspace",
     "mrp_film_mean_fwd_cl",
     "mrp_film_mean_bwd_cl",
@@ -115,6 +117,24 @@ class Epilogue(ctypes.Structure):
                 ("xcopy_node_stride", ctypes.c_int64)]
 
 
+#: enum mrp_agg_kernel: the kernel a launch plan names
+AGG_KERNELS = ("none", "film_fwd", "film_fwd_regular", "film_bwd_fused", "film_bwd_dx_gram", "film_bwd_regular",
+               "film_bwd_mfma")
+
+
+class AggPlan(ctypes.Structure):
+    """``mrp_agg_plan``: what ``mrp_film_mean_fwd_plan`` / ``mrp_film_mean_bwd_plan`` report (no GPU call)."""
+
+    _fields_ = [("kernel", ctypes.c_int32), ("vec", ctypes.c_int32), ("lpc", ctypes.c_int32),
+                ("cpb", ctypes.c_int32), ("threads", ctypes.c_int32), ("psplit", ctypes.c_int32),
+                ("ncb", ctypes.c_int32), ("pre2", ctypes.c_int32), ("grid", ctypes.c_int64),
+                ("lds_bytes", ctypes.c_int64)]
+
+    @property
+    def kernel_name(self) -> str:
+        return AGG_KERNELS[self.kernel]
+
+
 class EpilogueCl(ctypes.Structure):
     """``mrp_agg_epilogue_cl``: ``Epilogue`` plus the pixel strides of x0 and xcopy (pixel-major tensors)."""
 
@@ -146,6 +166,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_mean_fwd_t.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_t.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, ep, _P]
     lib.mrp_film_mean_bwd_t.restype = ctypes.c_int
+    plan = ctypes.POINTER(AggPlan)
+    lib.mrp_film_mean_fwd_plan.argtypes = [_I32, _P, _I64, _P] + graph + [_P, _I64, ep, plan]
+    lib.mrp_film_mean_fwd_plan.restype = ctypes.c_int
+    lib.mrp_film_mean_bwd_plan.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, ep, plan]
+    lib.mrp_film_mean_bwd_plan.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32]
     lib.mrp_film_mean_bwd_workspace.restype = ctypes.c_int64
     epc = ctypes.POINTER(EpilogueCl)

@@ -429,6 +429,42 @@ def _mode_flags(mode, logits: bool) -> int:
     return m
 
 
+def launch_plan(direction: str, graph, C: int, P: int, dtype=torch.float32, mode="film_mean", logits: bool = False,
+                align: int = 16, grad_x_base: bool = False, need_dx: bool = True, need_dgb: bool = True,
+                x0: bool = False, xcopy: bool = False, stride: Optional[int] = None) -> _lib.AggPlan:
+    """The launch plan (``mrp_film_mean_fwd_plan`` / ``_bwd_plan``: kernel, slice width, lanes per plane,
+    channels per workgroup, LDS ...) of the ``"fwd"`` or ``"bwd"`` aggregation under the current tuning
+    knobs, for dense (N, C, H*W = P) tensors whose storage is aligned to ``align`` bytes.  ``graph`` is
+    anything with ``num_graphs``, ``max_nodes``, ``graph_kind``, ``num_nodes`` and ``num_edges`` (a
+    ``GraphCSR``).  Host-only: no tensor is needed and no GPU call is made — the library looks at pointers
+    for their alignment alone, so made-up ones stand in.  x0 / xcopy: the forward epilogue's extra tensors."""
+    base = 1 << 20
+    p = ctypes.c_void_p(base if align % 16 == 0 else base + align)
+    null = ctypes.c_void_p(0)
+    ns = C * P if stride is None else stride
+    m = _mode_flags(mode, logits)
+    copy = (m & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN
+    args = (null if copy else p, p, p, p, p, graph.num_graphs, graph.max_nodes, graph.graph_kind, graph.num_nodes,
+            graph.num_edges, C, P, m)
+    plan = _lib.AggPlan()
+    lib = _lib.load_library()
+    if direction == "fwd":
+        ep = None
+        if x0 or xcopy:
+            ep = _lib.Epilogue(1.0, 0.0, p.value if x0 else 0, ns, 0.5 if x0 else 0.0, p.value if xcopy else 0, ns)
+        code = lib.mrp_film_mean_fwd_plan(FEATURE_DTYPES[dtype], p, ns, *args, p, ns,
+                                          ctypes.byref(ep) if ep is not None else None, ctypes.byref(plan))
+        _lib.check(code, "mrp_film_mean_fwd_plan")
+    elif direction == "bwd":
+        code = lib.mrp_film_mean_bwd_plan(FEATURE_DTYPES[dtype], p, ns, p, ns, *args, p if need_dx else null, ns,
+                                          p if (grad_x_base and need_dx) else null, ns, p if need_dgb else null,
+                                          None, ctypes.byref(plan))
+        _lib.check(code, "mrp_film_mean_bwd_plan")
+    else:
+        raise ValueError(f"direction must be 'fwd' or 'bwd', got {direction!r}")
+    return plan
+
+
 def _check_x(x):
     if x.dim() != 4:
         raise ValueError(f"node features must be (N, C, H, W), got {tuple(x.shape)}")

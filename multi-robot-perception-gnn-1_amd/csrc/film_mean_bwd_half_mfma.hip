@@ -10,7 +10,7 @@ namespace {
 // launch_bwd_mfma_k for storage type T, 16-node blocks (g.cpb = 4 x blocks per wave)
 template <typename T, bool COMPLETE, int KMAX>
 hipError_t launch_bwd_half_mfma_k(const AggArgs& a, const Geometry& g, hipStream_t st) {
-  const size_t lds = lds_mfma(g.cpb, 16, KMAX);
+  const size_t lds = g.lds;
   const int cpw = g.cpb / 4;
   if (a.dxb) {
     if (cpw == 1)
@@ -32,8 +32,8 @@ template <typename T>
 hipError_t launch_bwd_half_mfma(bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
   if (g.mfma_npb != 16 || (g.cpb != 4 && g.cpb != 8)) return hipErrorInvalidValue;
   if (complete) return launch_bwd_half_mfma_k<T, true, 1>(a, g, st);
-  if (a.kdeg >= 1 && a.kdeg <= 4) return launch_bwd_half_mfma_k<T, false, 4>(a, g, st);
-  if (a.kdeg >= 5 && a.kdeg <= 8) return launch_bwd_half_mfma_k<T, false, 8>(a, g, st);
+  if (g.kmax == 4) return launch_bwd_half_mfma_k<T, false, 4>(a, g, st);
+  if (g.kmax == 8) return launch_bwd_half_mfma_k<T, false, 8>(a, g, st);
   return hipErrorInvalidValue;
 }
 

@@ -8,11 +8,8 @@ template <int NT, bool COMPLETE, bool DXB>
 hipError_t launch_bwd_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st) {
   if constexpr (NT <= 8) {
     const AggArgs& a = a_in;
-    const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits, g.lpc);
-    // exactly two slices per lane: both prefetched (film_bwd_fused PRE2; bwd_pre2 = 2: not with a
-    // grad_x base, whose instantiation then prefetches the base rows instead)
-    const int pre2 = tuning().bwd_pre2;
-    if (g.vec == 4 && a.PV == 2 * g.lpc && (pre2 == 1 || (pre2 == 2 && !DXB))) {
+    const size_t lds = g.lds;
+    if (g.pre2) {  // exactly two slices per lane, both prefetched (film_bwd_plan)
       MRP_LAUNCH((mrp::film_bwd_fused<NT, NT, 4, COMPLETE, DXB, 1, true>), lds);
       return hipGetLastError();
     }
@@ -26,7 +23,7 @@ hipError_t launch_bwd_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st
   } else {
     if (a_in.want_dx) {
       const AggArgs& a = a_in;
-      const size_t lds = lds_dx<NT>(g.cpb);
+      const size_t lds = g.lds_dx;
       if (g.vec == 4)
         MRP_LAUNCH((mrp::film_bwd_dx<NT, 4, COMPLETE, DXB>), lds);
       else if (g.vec == 2)
@@ -39,7 +36,7 @@ hipError_t launch_bwd_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st
     if (a_in.want_dgb) {
       AggArgs a = a_in;
       a.want_dx = 0;
-      const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits);
+      const size_t lds = g.lds;
       if (g.vec == 4)
         MRP_LAUNCH((mrp::film_bwd_fused<NT, 4, 4, COMPLETE>), lds);
       else if (g.vec == 2)
@@ -60,7 +57,7 @@ template <typename T, int NT, bool COMPLETE, bool DXB>
 hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream_t st) {
   if constexpr (NT <= 8) {
     const AggArgs& a = a_in;
-    const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits, g.lpc);
+    const size_t lds = g.lds;
     if (g.vec == 4)
       MRP_LAUNCH((mrp::film_bwd_fused<NT, NT, 4, COMPLETE, DXB, 1, false, T>), lds);
     else
@@ -69,7 +66,7 @@ hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream
   } else {
     if (a_in.want_dx) {
       const AggArgs& a = a_in;
-      const size_t lds = lds_dx<NT>(g.cpb);
+      const size_t lds = g.lds_dx;
       if (g.vec == 4)
         MRP_LAUNCH((mrp::film_bwd_dx<NT, 4, COMPLETE, DXB, T>), lds);
       else
@@ -80,7 +77,7 @@ hipError_t launch_bwd_half_ntb(const AggArgs& a_in, const Geometry& g, hipStream
     if (a_in.want_dgb) {
       AggArgs a = a_in;
       a.want_dx = 0;
-      const size_t lds = lds_bwd<NT>(g.cpb, COMPLETE && a.logits);
+      const size_t lds = g.lds;
       if (g.vec == 4)
         MRP_LAUNCH((mrp::film_bwd_fused<NT, 4, 4, COMPLETE, false, 1, false, T>), lds);
       else
@@ -98,7 +95,7 @@ hipError_t launch_bwd_half_mfma(bool complete, const AggArgs& a, const Geometry&
 
 template <typename T, int NT>
 hipError_t launch_bwd_half_nt(bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
-  if (g.mfma_npb) {
+  if (g.kernel == MRP_AGG_KERNEL_FILM_BWD_MFMA) {
     if constexpr (NT > 8) return launch_bwd_half_mfma<T>(complete, a, g, st);
     return hipErrorInvalidValue;  // graphs of <= 8 nodes run film_bwd_fused
   }
@@ -117,7 +114,7 @@ hipError_t launch_bwd_half_nt(bool complete, const AggArgs& a, const Geometry& g
 template <int NT, int KMAX, bool DXB>
 hipError_t launch_bwd_regular(const AggArgs& a, const Geometry& g, hipStream_t st) {
   // VEC 4 would need 4*NT registers more per operand and spills; KMAX 8 only fits at VEC 1
-  const size_t lds = lds_regular<NT, KMAX>(g.cpb);
+  const size_t lds = g.lds;
   bool done = false;
   if constexpr (KMAX <= 4) {
     if (g.vec == 2) {
@@ -133,7 +130,7 @@ hipError_t launch_bwd_regular(const AggArgs& a, const Geometry& g, hipStream_t s
 // channels per block)
 template <bool COMPLETE, int NPB, int KMAX>
 hipError_t launch_bwd_mfma_k(const AggArgs& a, const Geometry& g, hipStream_t st) {
-  const size_t lds = lds_mfma(g.cpb, NPB, KMAX);
+  const size_t lds = g.lds;
   const int cpw = g.cpb / (4 * (16 / NPB));
   if (a.dxb) {
     if (cpw == 1)
@@ -157,8 +154,8 @@ hipError_t launch_bwd_mfma(const AggArgs& a, const Geometry& g, hipStream_t st) 
     return hipErrorInvalidValue;  // complete graphs of <= 8 nodes run film_bwd_fused
   } else {
     if constexpr (NT > 8) {
-      if (a.kdeg >= 1 && a.kdeg <= 4) return launch_bwd_mfma_k<false, 16, 4>(a, g, st);
-      if (a.kdeg >= 5 && a.kdeg <= 8) return launch_bwd_mfma_k<false, 16, 8>(a, g, st);
+      if (g.kmax == 4) return launch_bwd_mfma_k<false, 16, 4>(a, g, st);
+      if (g.kmax == 8) return launch_bwd_mfma_k<false, 16, 8>(a, g, st);
     }
     return hipErrorInvalidValue;
   }
@@ -166,14 +163,20 @@ hipError_t launch_bwd_mfma(const AggArgs& a, const Geometry& g, hipStream_t st) 
 
 template <int NT, bool COMPLETE>
 hipError_t launch_bwd_nt(const AggArgs& a, const Geometry& g, hipStream_t st) {
-  if (g.mfma_npb) return launch_bwd_mfma<NT, COMPLETE>(a, g, st);
-  if constexpr (NT > 8 && !COMPLETE) {
+  // the kernel film_bwd_plan chose
+  if (g.kernel == MRP_AGG_KERNEL_FILM_BWD_MFMA) return launch_bwd_mfma<NT, COMPLETE>(a, g, st);
+  if (g.kernel == MRP_AGG_KERNEL_FILM_BWD_REGULAR) {
     // regular in-degree (k-NN): per-edge-slot Gram, one sweep
-    if (a.kdeg >= 1 && a.kdeg <= 4)
-      return a.dxb ? launch_bwd_regular<NT, 4, true>(a, g, st) : launch_bwd_regular<NT, 4, false>(a, g, st);
-    if (a.kdeg >= 5 && a.kdeg <= 8)
-      return a.dxb ? launch_bwd_regular<NT, 8, true>(a, g, st) : launch_bwd_regular<NT, 8, false>(a, g, st);
+    if constexpr (NT > 8 && !COMPLETE) {
+      if (g.kmax == 4)
+        return a.dxb ? launch_bwd_regular<NT, 4, true>(a, g, st) : launch_bwd_regular<NT, 4, false>(a, g, st);
+      if (g.kmax == 8)
+        return a.dxb ? launch_bwd_regular<NT, 8, true>(a, g, st) : launch_bwd_regular<NT, 8, false>(a, g, st);
+    }
+    return hipErrorInvalidValue;
   }
+  if (g.kernel != (NT <= 8 ? MRP_AGG_KERNEL_FILM_BWD_FUSED : MRP_AGG_KERNEL_FILM_BWD_DX_GRAM))
+    return hipErrorInvalidValue;
   return a.dxb ? launch_bwd_ntb<NT, COMPLETE, true>(a, g, st) : launch_bwd_ntb<NT, COMPLETE, false>(a, g, st);
 }
 

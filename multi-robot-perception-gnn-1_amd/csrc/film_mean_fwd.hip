@@ -21,6 +21,116 @@ Tuning& tuning() {
   static Tuning t;
   return t;
 }
+
+int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float* gb, const int32_t* indptr,
+                  const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs,
+                  int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
+                  int32_t mode_flags, void* out, int64_t out_node_stride, const mrp_agg_epilogue* ep, AggArgs& a,
+                  Geometry& g) {
+  g = Geometry();  // kernel = MRP_AGG_KERNEL_NONE until a launch is planned
+  const bool half = elem == 2;  // 16-bit features (kHalfIo)
+  void* xcopy = ep != nullptr ? ep->xcopy : nullptr;
+  const int64_t xcopy_node_stride = ep != nullptr ? ep->xcopy_node_stride : 0;
+  const void* x0 = ep != nullptr ? ep->x0 : nullptr;
+  const int64_t x0_node_stride = ep != nullptr ? ep->x0_node_stride : 0;
+  const int32_t logits = (mode_flags & MRP_AGG_GB_LOGITS) ? 1 : 0;
+  const int32_t mode = mode_flags & ~MRP_AGG_GB_LOGITS;
+  if (!common_args_ok(indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P,
+                      mode))
+    return hipErrorInvalidValue;
+  if (num_graphs == 0 || num_nodes == 0 || max_nodes == 0 || C == 0 || P == 0) return hipSuccess;
+  const int64_t plane = (int64_t)C * P;
+  if (x == nullptr || out == nullptr || x_node_stride < plane || out_node_stride < plane)
+    return hipErrorInvalidValue;
+  if (mode != MRP_AGG_COPY_MEAN && num_edges > 0 && gb == nullptr) return hipErrorInvalidValue;
+  if (xcopy != nullptr && xcopy_node_stride < plane) return hipErrorInvalidValue;
+  if (x0 != nullptr && x0_node_stride < plane) return hipErrorInvalidValue;
+  SliceCheck sc;
+  sc.strides = P;
+  sc.add(x, x_node_stride);
+  sc.add(out, out_node_stride);
+  if (xcopy != nullptr) sc.add(xcopy, xcopy_node_stride);
+  if (x0 != nullptr) sc.add(x0, x0_node_stride);
+  const int32_t kdeg = MRP_GRAPH_IS_REGULAR(graph_kind) ? MRP_GRAPH_REGULAR_K(graph_kind) : 0;
+  const bool regular = kdeg >= 1 && kdeg <= 8;
+  const Tuning& tu = tuning();
+  int fvec, rvec;  // slice width of film_fwd / film_fwd_regular
+  if (half) {
+    // 16-byte slices of 8 elements (graphs of <= 8 nodes: beyond, 8 slices of 16 sources are 128 live
+    // registers before the first product), else 8-byte slices of 4, else single elements
+    fvec = rvec = (max_nodes <= 8 && sc.ok(8, elem)) ? 8 : (sc.ok(4, elem) ? 4 : 1);
+  } else {
+    // 16-byte slices beat 8-byte ones at every measured size (tools/kernel_lab.hip product sweep)
+    const bool vec4 = sc.ok(4, elem);
+    fvec = vec4 ? (P < tu.fwd_vec2_below ? 2 : 4) : 1;
+    rvec = vec4 ? 4 : 1;
+  }
+  g = regular ? make_geometry(C, P, rvec, tu.fwd_regular_lo, tu.fwd_regular_hi, tu.fwd_regular_cap)
+              : make_geometry(C, P, fvec, tu.fwd_lo, tu.fwd_hi, tu.fwd_cap);
+  g.kernel = regular ? MRP_AGG_KERNEL_FILM_FWD_REGULAR : MRP_AGG_KERNEL_FILM_FWD;
+  g.kmax = regular ? (kdeg <= 4 ? 4 : 8) : 0;
+  // (at most 16 channels of 16-node tiles: 33 KiB, under kMaxDynamicLds at every setting)
+  g.lds = regular ? lds_fwd_regular(max_nodes, g.kmax, g.cpb) : lds_fwd(max_nodes, g.cpb);
+  // COMPLETE graphs: one slice per lane, the plane split over ceil(PV / lpc) workgroups (their
+  // prologue is one round of independent gamma/beta loads, hidden under the first slice).  CSR
+  // graphs keep whole planes: their prologue walks the CSR (dependent loads) and a split repeats it
+  // per segment (k-NN(4) N=16 C=1024 16x16: 304 us split vs 225 us whole)
+  const int32_t pv = P / g.vec;
+  g.psplit = (graph_kind == MRP_GRAPH_COMPLETE || (regular && tu.fwd_regular_split)) ? (pv + g.lpc - 1) / g.lpc : 1;
+  g.grid = (int64_t)num_graphs * g.ncb * g.psplit;
+  if (g.grid > 0x7fffffff) return hipErrorInvalidValue;
+  a = {};
+  a.x = x;
+  a.xs = x_node_stride;
+  a.gb = gb;
+  a.indptr = indptr;
+  a.src = src;
+  a.eid = eid;
+  a.goff = graph_off;
+  a.out = out;
+  a.os = out_node_stride;
+  a.C = C;
+  a.P = P;
+  a.PV = P / g.vec;
+  a.mode = mode;
+  a.lpc = g.lpc;
+  a.cpb = g.cpb;
+  a.ncb = g.ncb;
+  a.logits = logits;
+  a.xc = xcopy;
+  a.xcs = xcopy_node_stride;
+  a.psplit = g.psplit;
+  a.kdeg = kdeg;
+  a.agg_scale = 1.f;
+  if (ep != nullptr) {
+    a.agg_scale = ep->agg_scale;
+    a.self_scale = ep->self_scale;
+    a.x0 = x0;
+    a.x0s = x0_node_stride;
+    a.x0_scale = ep->x0_scale;
+    a.epi = (ep->agg_scale != 1.f || ep->self_scale != 0.f || x0 != nullptr) ? 1 : 0;
+  }
+  return hipSuccess;
+}
+
+// A planner's result as the C ABI's mrp_agg_plan.
+void fill_plan(const Geometry& g, int want_dx, int want_dgb, mrp_agg_plan* plan) {
+  *plan = {};
+  plan->kernel = g.kernel;
+  if (g.kernel == MRP_AGG_KERNEL_NONE) return;
+  plan->vec = g.vec;
+  plan->lpc = g.lpc;
+  plan->cpb = g.cpb;
+  plan->threads = g.threads;
+  plan->psplit = g.psplit;
+  plan->ncb = g.ncb;
+  plan->pre2 = g.pre2;
+  plan->grid = g.grid;
+  size_t lds = g.lds;
+  if (g.kernel == MRP_AGG_KERNEL_FILM_BWD_DX_GRAM)  // the launches made: film_bwd_dx and / or the Gram pass
+    lds = std::max(want_dx ? g.lds_dx : (size_t)0, want_dgb ? g.lds : (size_t)0);
+  plan->lds_bytes = (int64_t)lds;
+}
 }  // namespace mrp_host
 
 extern "C" {
@@ -168,6 +278,22 @@ int mrp_film_mean_fwd_t(int32_t dtype, const void* x, int64_t x_node_stride, con
                           num_nodes, num_edges, C, P, mode_flags, out, out_node_stride, epilogue, stream);
     default: return hipErrorInvalidValue;
   }
+}
+
+int mrp_film_mean_fwd_plan(int32_t dtype, const void* x, int64_t x_node_stride, const float* gb,
+                           const int32_t* indptr, const int32_t* src, const int32_t* eid, const int32_t* graph_off,
+                           int32_t num_graphs, int32_t max_nodes, int32_t graph_kind, int32_t num_nodes,
+                           int32_t num_edges, int32_t C, int32_t P, int32_t mode_flags, void* out,
+                           int64_t out_node_stride, const mrp_agg_epilogue* epilogue, mrp_agg_plan* plan) {
+  if (plan == nullptr) return hipErrorInvalidValue;
+  if (dtype != MRP_DTYPE_F32 && dtype != MRP_DTYPE_BF16 && dtype != MRP_DTYPE_F16) return hipErrorInvalidValue;
+  AggArgs a = {};
+  Geometry g;
+  const int rc = film_fwd_plan(dtype == MRP_DTYPE_F32 ? 4 : 2, x, x_node_stride, gb, indptr, src, eid, graph_off,
+                               num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P, mode_flags, out,
+                               out_node_stride, epilogue, a, g);
+  if (rc == hipSuccess) fill_plan(g, 0, 0, plan);
+  return rc;
 }
 
 }  // extern "C"

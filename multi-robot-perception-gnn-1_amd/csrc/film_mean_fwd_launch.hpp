@@ -14,7 +14,7 @@ constexpr bool kHalfIo = sizeof(T) == 2;
 
 template <typename T, int NT, int KMAX>
 hipError_t launch_fwd_regular(const AggArgs& a, const Geometry& g, hipStream_t st) {
-  const size_t lds = lds_fwd_regular<NT, KMAX>(g.cpb);
+  const size_t lds = g.lds;
   if constexpr (kHalfIo<T>) {
     if (g.vec == 8 && NT <= 8) {
       if constexpr (NT <= 8) MRP_LAUNCH((mrp::film_fwd_regular<NT, KMAX, 8, 0, T>), lds);
@@ -45,12 +45,16 @@ hipError_t launch_fwd_regular(const AggArgs& a, const Geometry& g, hipStream_t s
 
 template <typename T, int NT, bool COMPLETE>
 hipError_t launch_fwd_nt(const AggArgs& a, const Geometry& g, hipStream_t st) {
-  if constexpr (!COMPLETE) {
+  if (g.kernel == MRP_AGG_KERNEL_FILM_FWD_REGULAR) {
     // per-edge-slot weights for uniform in-degree (k-NN frames)
-    if (a.kdeg >= 1 && a.kdeg <= 4) return launch_fwd_regular<T, NT, 4>(a, g, st);
-    if (a.kdeg >= 5 && a.kdeg <= 8) return launch_fwd_regular<T, NT, 8>(a, g, st);
+    if constexpr (!COMPLETE) {
+      if (g.kmax == 4) return launch_fwd_regular<T, NT, 4>(a, g, st);
+      if (g.kmax == 8) return launch_fwd_regular<T, NT, 8>(a, g, st);
+    }
+    return hipErrorInvalidValue;
   }
-  const size_t lds = lds_fwd<NT>(g.cpb);
+  if (g.kernel != MRP_AGG_KERNEL_FILM_FWD) return hipErrorInvalidValue;
+  const size_t lds = g.lds;
   if constexpr (kHalfIo<T>) {
     if constexpr (COMPLETE && NT >= 2 && NT <= 8) {
       if (g.vec == 8 && a.mode == MRP_AGG_FILM_MEAN) {
@@ -116,6 +120,17 @@ struct SliceCheck {
   bool ok(int vec, size_t elem) const { return strides % vec == 0 && ptrs % (vec * elem) == 0; }
 };
 
+// The forward's launch plan (film_mean_fwd.hip): validation, kernel choice, slice width, geometry, plane
+// split and dynamic LDS for features of `elem` bytes per element.  No GPU call; the pointers are looked
+// at for alignment and NULL only.  Returns the code the entry points return before launching;
+// g.kernel == MRP_AGG_KERNEL_NONE with hipSuccess: nothing to launch.  Behind both film_fwd_impl and
+// mrp_film_mean_fwd_plan.
+int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float* gb, const int32_t* indptr,
+                  const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs,
+                  int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
+                  int32_t mode_flags, void* out, int64_t out_node_stride, const mrp_agg_epilogue* ep, AggArgs& a,
+                  Geometry& g);
+
 // The forward behind mrp_film_mean_fwd{,_ex,_t} and mrp_film_mean_cat_fwd; x, out and the epilogue's
 // x0 / xcopy hold elements of T, strides in elements.
 template <typename T>
@@ -123,85 +138,11 @@ int film_fwd_impl(const T* x, int64_t x_node_stride, const float* gb, const int3
                   const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
                   int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t mode_flags,
                   T* out, int64_t out_node_stride, const mrp_agg_epilogue* ep, void* stream) {
-  T* xcopy = ep != nullptr ? reinterpret_cast<T*>(ep->xcopy) : nullptr;
-  const int64_t xcopy_node_stride = ep != nullptr ? ep->xcopy_node_stride : 0;
-  const T* x0 = ep != nullptr ? reinterpret_cast<const T*>(ep->x0) : nullptr;
-  const int64_t x0_node_stride = ep != nullptr ? ep->x0_node_stride : 0;
-  const int32_t logits = (mode_flags & MRP_AGG_GB_LOGITS) ? 1 : 0;
-  const int32_t mode = mode_flags & ~MRP_AGG_GB_LOGITS;
-  if (!common_args_ok(indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P,
-                      mode))
-    return hipErrorInvalidValue;
-  if (num_graphs == 0 || num_nodes == 0 || max_nodes == 0 || C == 0 || P == 0) return hipSuccess;
-  const int64_t plane = (int64_t)C * P;
-  if (x == nullptr || out == nullptr || x_node_stride < plane || out_node_stride < plane)
-    return hipErrorInvalidValue;
-  if (mode != MRP_AGG_COPY_MEAN && num_edges > 0 && gb == nullptr) return hipErrorInvalidValue;
-  if (xcopy != nullptr && xcopy_node_stride < plane) return hipErrorInvalidValue;
-  if (x0 != nullptr && x0_node_stride < plane) return hipErrorInvalidValue;
-  SliceCheck sc;
-  sc.strides = P;
-  sc.add(x, x_node_stride);
-  sc.add(out, out_node_stride);
-  if (xcopy != nullptr) sc.add(xcopy, xcopy_node_stride);
-  if (x0 != nullptr) sc.add(x0, x0_node_stride);
-  const int32_t kdeg = MRP_GRAPH_IS_REGULAR(graph_kind) ? MRP_GRAPH_REGULAR_K(graph_kind) : 0;
-  const bool regular = kdeg >= 1 && kdeg <= 8;
-  const Tuning& tu = tuning();
-  int fvec, rvec;  // slice width of film_fwd / film_fwd_regular
-  if constexpr (kHalfIo<T>) {
-    // 16-byte slices of 8 elements (graphs of <= 8 nodes: beyond, 8 slices of 16 sources are 128 live
-    // registers before the first product), else 8-byte slices of 4, else single elements
-    fvec = rvec = (max_nodes <= 8 && sc.ok(8, sizeof(T))) ? 8 : (sc.ok(4, sizeof(T)) ? 4 : 1);
-  } else {
-    // 16-byte slices beat 8-byte ones at every measured size (tools/kernel_lab.hip product sweep)
-    const bool vec4 = sc.ok(4, sizeof(T));
-    fvec = vec4 ? (P < tu.fwd_vec2_below ? 2 : 4) : 1;
-    rvec = vec4 ? 4 : 1;
-  }
-  Geometry g = regular ? make_geometry(C, P, rvec, tu.fwd_regular_lo, tu.fwd_regular_hi, tu.fwd_regular_cap)
-                       : make_geometry(C, P, fvec, tu.fwd_lo, tu.fwd_hi, tu.fwd_cap);
-  // COMPLETE graphs: one slice per lane, the plane split over ceil(PV / lpc) workgroups (their
-  // prologue is one round of independent gamma/beta loads, hidden under the first slice).  CSR
-  // graphs keep whole planes: their prologue walks the CSR (dependent loads) and a split repeats it
-  // per segment (k-NN(4) N=16 C=1024 16x16: 304 us split vs 225 us whole)
-  const int32_t pv = P / g.vec;
-  const int32_t psplit = (graph_kind == MRP_GRAPH_COMPLETE || (regular && tu.fwd_regular_split))
-                             ? (pv + g.lpc - 1) / g.lpc
-                             : 1;
-  g.grid = (int64_t)num_graphs * g.ncb * psplit;
-  if (g.grid > 0x7fffffff) return hipErrorInvalidValue;
   AggArgs a = {};
-  a.x = x;
-  a.xs = x_node_stride;
-  a.gb = gb;
-  a.indptr = indptr;
-  a.src = src;
-  a.eid = eid;
-  a.goff = graph_off;
-  a.out = out;
-  a.os = out_node_stride;
-  a.C = C;
-  a.P = P;
-  a.PV = P / g.vec;
-  a.mode = mode;
-  a.lpc = g.lpc;
-  a.cpb = g.cpb;
-  a.ncb = g.ncb;
-  a.logits = logits;
-  a.xc = xcopy;
-  a.xcs = xcopy_node_stride;
-  a.psplit = psplit;
-  a.kdeg = kdeg;
-  a.agg_scale = 1.f;
-  if (ep != nullptr) {
-    a.agg_scale = ep->agg_scale;
-    a.self_scale = ep->self_scale;
-    a.x0 = x0;
-    a.x0s = x0_node_stride;
-    a.x0_scale = ep->x0_scale;
-    a.epi = (ep->agg_scale != 1.f || ep->self_scale != 0.f || x0 != nullptr) ? 1 : 0;
-  }
+  Geometry g;
+  const int rc = film_fwd_plan(sizeof(T), x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs, max_nodes,
+                               graph_kind, num_nodes, num_edges, C, P, mode_flags, out, out_node_stride, ep, a, g);
+  if (rc != hipSuccess || g.kernel == MRP_AGG_KERNEL_NONE) return rc;
   return dispatch_fwd<T>(max_nodes, graph_kind == MRP_GRAPH_COMPLETE, a, g, static_cast<hipStream_t>(stream));
 }
 

@@ -66,7 +66,10 @@ struct AggArgs {
   const void* dxb;  // bwd: optional grad_x base (added to grad_x), node stride dxbs
   int64_t dxbs;
   int32_t C, P, PV, mode;
-  int32_t lpc;  // lanes per channel plane (power of two <= 64; <= 256 in film_bwd_fused: lpc/64 waves)
+  // lanes per channel plane, a power of two: <= 256 in film_fwd, film_fwd_regular and film_bwd_dx (no lane
+  // of theirs reads another's values) and in film_bwd_fused (lpc/64 waves, one Gram partial each); <= 64 in
+  // film_bwd_regular and film_bwd_fused's VB = 4 Gram pass (with_lanes reduces over one wave at most)
+  int32_t lpc;
   int32_t cpb;  // channels per workgroup
   int32_t ncb;  // channel blocks per graph
   int32_t want_dx, want_dgb;
@@ -1998,9 +2001,18 @@ struct Geometry {
   int vec, lpc, cpb, threads, ncb;
   int64_t grid;
   int mfma_npb = 0;  // film_bwd_mfma: nodes per 16-row block (16 or 8); 0 = the VALU kernels
+  // the rest of the plan (film_fwd_plan / film_bwd_plan): what the launch templates act on
+  int kernel = MRP_AGG_KERNEL_NONE;  // mrp_agg_kernel
+  int kmax = 0;      // per-edge-slot kernels (regular graphs): compiled slot count per destination, 4 or 8
+  int psplit = 1;    // forward: plane segments per (graph, channel block)
+  int pre2 = 0;      // film_bwd_fused: the PRE2 instantiation (both of a lane's two slices prefetched)
+  size_t lds = 0;    // dynamic LDS of the kernel (MRP_AGG_KERNEL_FILM_BWD_DX_GRAM: of the Gram pass)
+  size_t lds_dx = 0; // MRP_AGG_KERNEL_FILM_BWD_DX_GRAM: dynamic LDS of film_bwd_dx
 };
 
-
+// Dynamic LDS a kernel may ask for without raising hipFuncAttributeMaxDynamicSharedMemorySize, which no
+// aggregation launcher does: the planners shrink a workgroup's channels until its request fits.
+constexpr size_t kMaxDynamicLds = 64 * 1024;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
@@ -2028,37 +2040,58 @@ inline Geometry make_geometry(int C, int P, int vec, int lo, int hi, int max_cpb
   return g;
 }
 
-template <int NT>
-size_t lds_fwd(int cpb) {
-  return (size_t)(2 * cpb * mrp::Tile<NT>::SZ + 2 * mrp::Tile<NT>::NTP) * sizeof(float);
+// Channels per workgroup of a planned geometry changed to cpb (same lanes per plane).
+inline void set_cpb(Geometry& g, int C, int cpb) {
+  g.cpb = cpb;
+  g.threads = cpb * g.lpc;
+  g.ncb = (C + cpb - 1) / cpb;
 }
-template <int NT, int KMAX>
-size_t lds_fwd_regular(int cpb) {
-  return (size_t)cpb * (NT * KMAX + 2) * sizeof(float2) + (size_t)NT * (KMAX / 4) * sizeof(unsigned);
+
+// mrp::Tile<nt>'s constants for a graph size known at run time (the planners size LDS with them).
+struct TileDims {
+  int NTP, SZ, SLS;
+};
+inline TileDims tile_dims(int nt) {
+  switch (nt) {
+#define MRP_TILE_CASE(N) \
+  case N: return {mrp::Tile<N>::NTP, mrp::Tile<N>::SZ, mrp::Tile<N>::SLS};
+    MRP_TILE_CASE(1) MRP_TILE_CASE(2) MRP_TILE_CASE(3) MRP_TILE_CASE(4) MRP_TILE_CASE(5) MRP_TILE_CASE(6)
+    MRP_TILE_CASE(7) MRP_TILE_CASE(8) MRP_TILE_CASE(9) MRP_TILE_CASE(10) MRP_TILE_CASE(11) MRP_TILE_CASE(12)
+    MRP_TILE_CASE(13) MRP_TILE_CASE(14) MRP_TILE_CASE(15) MRP_TILE_CASE(16)
+#undef MRP_TILE_CASE
+    default: return {0, 0, 0};
+  }
 }
-template <int NT>
-size_t lds_dx(int cpb) {
-  return (size_t)(cpb * mrp::Tile<NT>::SZ + mrp::Tile<NT>::NTP) * sizeof(float);
+
+// Dynamic LDS of each kernel for graphs of up to nt nodes (the layouts at the head of the kernels).
+inline size_t lds_fwd(int nt, int cpb) {
+  const TileDims t = tile_dims(nt);
+  return (size_t)(2 * cpb * t.SZ + 2 * t.NTP) * sizeof(float);
 }
-template <int NT, int KMAX>
-size_t lds_regular(int cpb) {
-  return (size_t)(cpb * mrp::Tile<NT>::SZ + cpb * NT * KMAX + cpb * mrp::Tile<NT>::NTP + mrp::Tile<NT>::NTP) *
-             sizeof(float) +
-         2 * (size_t)NT * KMAX * sizeof(int);
+inline size_t lds_fwd_regular(int nt, int kmax, int cpb) {
+  return (size_t)cpb * (nt * kmax + 2) * sizeof(float2) + (size_t)nt * (kmax / 4) * sizeof(unsigned);
+}
+inline size_t lds_dx(int nt, int cpb) {
+  const TileDims t = tile_dims(nt);
+  return (size_t)(cpb * t.SZ + t.NTP) * sizeof(float);
+}
+inline size_t lds_regular(int nt, int kmax, int cpb) {
+  const TileDims t = tile_dims(nt);
+  return (size_t)(cpb * t.SZ + cpb * nt * kmax + cpb * t.NTP + t.NTP) * sizeof(float) +
+         2 * (size_t)nt * kmax * sizeof(int);
 }
 // film_bwd_mfma: Wt/D + transpose tiles + S + slot table (cpb channels of npb nodes)
 inline size_t lds_mfma(int cpb, int npb, int kmax) {
   const int cs = npb * (npb + 1) + (npb == 16 ? 4 : 2);  // film_bwd_mfma's CS, TR, SS
   return (size_t)(cpb * cs + 4 * 16 * 40 + cpb * (npb + 1)) * sizeof(float) + 2 * (size_t)npb * kmax * sizeof(int);
 }
-template <int NT>
-size_t lds_bwd(int cpb, bool complete_logits, int lpc = 64) {
+inline size_t lds_bwd(int nt, int cpb, bool complete_logits, int lpc = 64) {
   // + the per-slot sigmoid values (float2) the COMPLETE epilogue reuses; one Gram partial per channel
   // group, or per wave when a plane spans several waves (lpc > 64)
+  const TileDims t = tile_dims(nt);
   const int npg = lpc > 64 ? cpb * (lpc >> 6) : cpb;
-  return (size_t)(cpb * mrp::Tile<NT>::SZ + npg * mrp::Tile<NT>::SZ + npg * mrp::Tile<NT>::SLS +
-                  mrp::Tile<NT>::NTP) * sizeof(float) +
-         (complete_logits ? (size_t)cpb * NT * NT * sizeof(float2) : 0);
+  return (size_t)(cpb * t.SZ + npg * t.SZ + npg * t.SLS + t.NTP) * sizeof(float) +
+         (complete_logits ? (size_t)cpb * nt * nt * sizeof(float2) : 0);
 }
 
 #define MRP_LAUNCH(KERNEL, LDS) hipLaunchKernelGGL((KERNEL), dim3((unsigned)g.grid), dim3(g.threads), (LDS), st, a)
@@ -2095,6 +2128,8 @@ inline bool common_args_ok(const int32_t* indptr, const int32_t* src, const int3
   case N: return COMPLETE ? FN<N, true>(__VA_ARGS__) : FN<N, false>(__VA_ARGS__);
 
 namespace mrp_host {
+// a planner's result as the C ABI's mrp_agg_plan (film_mean_fwd.hip; want_*: the backward's launches)
+void fill_plan(const Geometry& g, int want_dx, int want_dgb, mrp_agg_plan* plan);
 // backward dispatch, split over translation units by graph size (they compile in parallel)
 hipError_t dispatch_bwd_1_8(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 hipError_t dispatch_bwd_9_12(int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);

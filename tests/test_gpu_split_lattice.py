@@ -158,6 +158,25 @@ def test_encoder_forward_exact(cuda_device, variant, E, C, waves):
     sc.assert_bit_equal(z, c["z64"], f"z {variant} E={E} C={C} edge_split_v={waves}")
 
 
+@pytest.mark.parametrize("allx", [0, 1])
+@pytest.mark.parametrize("waves,C", [(1, 256), (1, 288), (3, 512), (3, 544)])
+@pytest.mark.parametrize("variant", ["three.bf16/three.bf16", "-/two.two"])
+def test_encoder_forward_exact_edge_allx(cuda_device, variant, waves, C, allx):
+    """``edge_allx`` (every hidden block before z, where ``C / 32 <= 2 nwv`` lets them fit LDS) on and off, at
+    the largest C that takes the form and the first above it, for 4 waves (nwv 4: C = 256 | 288) and 8 (512 |
+    544): the same exact product either way (``test_encoder_forward_exact``'s check, one ragged edge tile)."""
+    dev = cuda_device
+    E = 33
+    c = sc.encoder_case(E, C, variant)
+    t = _encoder_dev(c, dev)
+    z = torch.full((E, 2 * C), float("nan"), device=dev)
+    with _knobs(edge_split_v=waves, edge_allx=allx) as lib:
+        m._lib.check(lib.mrp_edge_encoder_fwd_split(_ptr(t["pose"]), _ptr(t["img"]), _ptr(t["b2"]), E, C, _ptr(z),
+                                                    _stream(dev)), "mrp_edge_encoder_fwd_split")
+        torch.cuda.synchronize()
+    sc.assert_bit_equal(z, c["z64"], f"z {variant} E={E} C={C} edge_split_v={waves} edge_allx={allx}")
+
+
 @pytest.mark.parametrize("waves", [1, 3])
 @pytest.mark.parametrize("E,C", [(33, 32), (96, 96), (33, 608)])
 @VARIANT

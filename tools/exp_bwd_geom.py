@@ -44,7 +44,10 @@ for cid in (2, 3):
                                                                                grad_x_base=bs) for G, xi, bs in sets]
         t = bench.time_launches(launches, 40, dev)
         byts = bench.alg_bytes_bwd(Nt, E, C, P, base=True)
-        res.append(f"{name} {t * 1e6:6.1f} us {byts / t / 8e12:5.3f}{'' if same else ' DIFF'}")
+        # the plan the knobs gave (a variant that collapses to the default geometry, or was clamped, shows here)
+        p = mrp.aggregate.launch_plan("bwd", csr, C, P, logits=True, grad_x_base=True)
+        plan = f"[{p.kernel_name} vec={p.vec} lpc={p.lpc} cpb={p.cpb} lds={p.lds_bytes}]"
+        res.append(f"{name} {t * 1e6:6.1f} us {byts / t / 8e12:5.3f} {plan}{'' if same else ' DIFF'}")
     lib.mrp_tuning_set(b"reset", 0)
     print(f"configs[{cid}]: " + " | ".join(res), flush=True)
     del sets

@@ -133,7 +133,7 @@ int main(int argc, char** argv) {
       mrp::AggArgs a = {};
       a.x = x; a.xs = (int64_t)C * P; a.gb = gb; a.out = out; a.os = (int64_t)C * P; a.C = C; a.P = P; a.PV = P / 4;
       a.mode = MRP_AGG_FILM_MEAN; a.logits = 1; a.lpc = lpc; a.cpb = cpb; a.ncb = (C + cpb - 1) / cpb; a.psplit = ps;
-      const size_t lds = mrp_host::lds_fwd<8>(cpb);
+      const size_t lds = mrp_host::lds_fwd(8, cpb);
       const unsigned grid = (unsigned)(B * a.ncb * ps);
       snprintf(nm, sizeof nm, "film_fwd lpc=%d cpb=%d psplit=%d grid=%u", lpc, cpb, ps, grid);
       report(nm, time_ms([&] { hipLaunchKernelGGL((mrp::film_fwd<8, 4, true>), dim3(grid), dim3(lpc * cpb), lds, 0, a); }, iters), alg);
@@ -158,7 +158,7 @@ int main(int argc, char** argv) {
       a.x = x; a.xs = (int64_t)C * P; a.g = gout; a.gs = (int64_t)C * P; a.gb = gb; a.out = dx; a.os = (int64_t)C * P;
       a.dgb = dgb; a.C = C; a.P = P; a.PV = P / 4; a.mode = MRP_AGG_FILM_MEAN; a.logits = 1; a.lpc = lpc; a.cpb = cpb;
       a.ncb = (C + cpb - 1) / cpb; a.want_dx = 1; a.want_dgb = 1;
-      const size_t lds = mrp_host::lds_bwd<8>(cpb, true, lpc);
+      const size_t lds = mrp_host::lds_bwd(8, cpb, true, lpc);
       const unsigned grid = (unsigned)(B * a.ncb);
       snprintf(nm, sizeof nm, "film_bwd_fused lpc=%d cpb=%d grid=%u", lpc, cpb, grid);
       report(nm, time_ms([&] { hipLaunchKernelGGL((mrp::film_bwd_fused<8, 8, 4, true, false, 1>), dim3(grid), dim3(lpc * cpb), lds, 0, a); }, iters), balg);

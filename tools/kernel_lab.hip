@@ -259,7 +259,7 @@ int main(int argc, char** argv) {
     const mrp_host::Geometry g = mrp_host::make_geometry(C, P, 4, 16, 64, mrp::kMaxChanPerBlock);
     mrp::AggArgs a = args_for(g.lpc, g.cpb);
     const int grid = B * a.ncb;
-    const size_t base = mrp_host::lds_fwd<8>(g.cpb);
+    const size_t base = mrp_host::lds_fwd(8, g.cpb);
     for (int cap : {0, 2, 3, 4, 5, 6, 8}) {
       const size_t lds = cap ? std::max(base, (size_t)(160 * 1024 / cap) - 256) : base;
       char nm[64];
@@ -350,7 +350,7 @@ int main(int argc, char** argv) {
 #define RVAR(NT, VEC, LPC)                                                                               \
     if (N == NT) {                                                                                       \
       mrp::AggArgs a = rargs(VEC, LPC);                                                                  \
-      const size_t lds_ = lds_regular<NT, 4>(a.cpb);                                                     \
+      const size_t lds_ = lds_regular(NT, 4, a.cpb);                                                     \
       float ms_ = time_ms([&] { hipLaunchKernelGGL((mrp::film_bwd_regular<NT, 4, VEC, false>),           \
                                                    dim3(B * a.ncb), dim3(a.cpb * LPC), lds_, 0, a); }, iters); \
       char nm_[96];                                                                                      \
@@ -420,7 +420,7 @@ int main(int argc, char** argv) {
       a.C = C; a.P = P; a.PV = P / vec; a.mode = 0; a.lpc = lpc; a.cpb = cpb; a.ncb = (C + cpb - 1) / cpb;
       a.logits = 1; a.g = gout; a.gs = (int64_t)C * P; a.dgb = dgb2; a.want_dx = 1; a.want_dgb = 1;
       const int grid = B * a.ncb;
-      const size_t lds = mrp_host::lds_bwd<8>(cpb, true);
+      const size_t lds = mrp_host::lds_bwd(8, cpb, true);
       float ms = time_ms([&] { hipLaunchKernelGGL(kern, dim3(grid), dim3(cpb * lpc), lds, 0, a); }, iters);
       char nm[96];
       snprintf(nm, sizeof nm, "bwd_fused vec=%d minw=%d lpc=%d cpb=%d", vec, minw, lpc, cpb);

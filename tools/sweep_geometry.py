@@ -69,6 +69,17 @@ def bwd_time(g, z, csr, need_dx=True, need_dgb=True):
     return t, alg_bytes_bwd(Nt, g.num_edges(), C, H * W) / t / 8e12
 
 
+def plan_text(label, g, csr):
+    """The launch plan under the knobs now set (mrp_film_mean_fwd_plan / _bwd_plan): a setting that collapses
+    to the default geometry, or that the planner clamped, shows here beside its timing."""
+    _, C, H, W = g.ndata["image"].shape
+    need = {"dx=1 dgb=0": (True, False), "dx=0 dgb=1": (False, True)}
+    dx, dgb = next((v for k, v in need.items() if k in label), (True, True))
+    p = mrp.aggregate.launch_plan("fwd" if label.startswith("fwd") else "bwd", csr, C, H * W, logits=True, need_dx=dx,
+                                  need_dgb=dgb)
+    return f"[{p.kernel_name} vec={p.vec} lpc={p.lpc} cpb={p.cpb} lds={p.lds_bytes}]"
+
+
 def sweep(label, name, fn, grid):
     g, z, csr = setup(name)
     keys = list(grid)
@@ -82,7 +93,7 @@ def sweep(label, name, fn, grid):
             print(f"{label} {name} {kw}: {e}", flush=True)
             continue
         res.append((t, kw, frac))
-        print(f"{label} {name:10s} {kw}  {t * 1e6:8.1f} us  {frac * 100:5.1f} %", flush=True)
+        print(f"{label} {name:10s} {kw}  {t * 1e6:8.1f} us  {frac * 100:5.1f} %  {plan_text(label, g, csr)}", flush=True)
     res.sort(key=lambda r: r[0])
     print(f"BEST {label} {name}: {res[0][1]} {res[0][0] * 1e6:.1f} us {res[0][2] * 100:.1f} %", flush=True)
     knobs()
@@ -118,7 +129,7 @@ def main():
         return
     if what == "cfg4bwd":  # k-NN backward: matrix-core kernel against the VALU kernel
         for _ in range(2):
-            sweep("bwd", "cfg4", bwd_time, {"bwd_regular_mfma": [0, 1], "bwd_mfma_cpw": [1, 2, 4]})
+            sweep("bwd", "cfg4", bwd_time, {"bwd_regular_mfma": [0, 1], "bwd_mfma_cpw": [1, 2]})
         for dx, dgb in ((True, False), (False, True)):
             sweep(f"bwd dx={int(dx)} dgb={int(dgb)}", "cfg4",
                   lambda g, z, csr, dx=dx, dgb=dgb: bwd_time(g, z, csr, dx, dgb), {"bwd_regular_mfma": [0, 1]})

@@ -681,8 +681,9 @@ int mrp_edge_encoder_fwd_split(const float* pose, const void* packed, const floa
 /*
  * The encoder's training path on the split-bf16 matrix cores (replaces mrp_edge_hidden_fwd +
  * mrp_edge_logits_fwd forward and the two library GEMMs of the backward, dgl/model/models.py:146-149
- * under dgl/training.py:208-210's loss.backward()):
- *   mrp_edge_encoder_fwd_split_train   as mrp_edge_encoder_fwd_split (shared-hidden form), and also
+ * under dgl/training.py:208-210's loss.backward(); the forward in encoder_split.hip, _bwd_prep / _bwd_t in
+ * edge_encoder.hip, _bwd_split / _bwd_fused in encoder_bwd_split.hip):
+ *   mrp_edge_encoder_fwd_split_train  as mrp_edge_encoder_fwd_split (shared-hidden form), and also
  *                                      h^T = relu(pose W1^T + b1)^T, (C, E) rows of hT_stride >= E floats
  *   mrp_edge_encoder_bwd_prep          dzT (2C, E) rows of dzT_stride >= E = dz^T (E % 4 == 0, C even,
  *                                      16-byte aligned, dzT_stride % 4 == 0; else hipErrorNotSupported)

@@ -19,12 +19,13 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "film_mean_fwd_f16.hip", "film_mean_bwd.hip",
                                                     "edge_encoder.hip", "frame_graph.hip",
                                                     "compress_gemm.hip", "encoder_split.hip",
-                                                    "compress_split.hip", "compress_half.hip",
+                                                    "compress_split.hip", "encoder_bwd_split.hip",
+                                                    "compress_half.hip",
                                                     "compress_split_cl.hip", "compress_half_cl.hip")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 HEADERS = [os.path.join(REPO, "include", "mrp_gnn.h")] + [os.path.join(PKG_DIR, "csrc", h) for h in (
     "film_mean_kernels.hpp", "film_mean_cl_kernels.hpp", "film_mean_bwd_launch.hpp", "film_mean_fwd_launch.hpp", "fast_math.hpp", "tuning.hpp", "encoder_split.hpp",
-    "compress_half_common.hpp", "gemm_common.hpp", "split_common.hpp")]
+    "compress_half_common.hpp", "gemm_common.hpp", "split_common.hpp", "split_nt.hpp")]
 OUT = os.path.join(PKG_DIR, "lib", "libmrp_gnn.so")
 ARCH = os.environ.get("MRP_OFFLOAD_ARCH", "gfx950")
 

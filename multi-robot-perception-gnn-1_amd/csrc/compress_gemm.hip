@@ -569,11 +569,7 @@ hipError_t launch_nn_cfg(NNArgs a, hipStream_t st) {
   a.mtiles = (a.M + G::TM - 1) / G::TM;
   const int64_t grid = (int64_t)a.mtiles * ((a.ncols + G::TN - 1) / G::TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nn<G>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_nn<G>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS, st, a);
-  return hipGetLastError();
+  return launch_lds<gemm_nn<G>>(G::LDS, dim3((unsigned)grid), dim3(G::THREADS), st, a);
 }
 
 hipError_t launch_nn(const NNArgs& a, hipStream_t st) { return launch_nn_cfg<V1>(a, st); }
@@ -630,11 +626,7 @@ hipError_t launch_nt_cfg(NTArgs a, int nsplit, hipStream_t st) {
   a.ntiles = (a.N + G::TN - 1) / G::TN;
   const int64_t grid = (int64_t)a.mtiles * a.ntiles * nsplit;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt<G>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_nt<G>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS, st, a);
-  return hipGetLastError();
+  return launch_lds<gemm_nt<G>>(G::LDS, dim3((unsigned)grid), dim3(G::THREADS), st, a);
 }
 
 hipError_t launch_nt(const NTArgs& a, int nsplit, hipStream_t st) { return launch_nt_cfg<V1>(a, nsplit, st); }

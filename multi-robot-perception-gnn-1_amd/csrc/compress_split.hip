@@ -1,12 +1,19 @@
-// compress_split.hip — the GCN layer's 1x1 compress convolution (forward and data gradient) on the
-// bf16 matrix cores at fp32 accuracy, gfx950 (MI355X / CDNA4).
+// compress_split.hip — the GCN layer's 1x1 compress convolution (forward, data gradient and weight
+// gradient) on the bf16 matrix cores at fp32 accuracy, gfx950 (MI355X / CDNA4).
 //
 // Reference (xjh19971/multi-robot-perception-gnn-1, dgl/model/models.py:163-165,181-184,186-189):
 //     h = self.conv1(torch.cat((h, g_h), dim=1))       # nn.Conv2d(2C, C, kernel_size=1), fp32
-// and its input gradient in training (dgl/training.py:208-210).  Per node n, with P = H W pixels:
+// and its gradients in training (dgl/training.py:208-210).  Per node n, with P = H W pixels:
 //     forward      y[n] = W [x[n]; a[n]] + b          M = C,  K = 2C (rows from x, then a)
 //     data grad    [dx[n]; da[n]] = W^T dy[n]         M = 2C, K = C  (rows to dx, then da)
-// the same NN product as compress_gemm.hip's gemm_nn (which runs it on the fp32 MFMA), here on
+//     weight grad  dW = sum_n dy[n] [x[n]; a[n]]^T, db = sum_n, pixels dy[n]     K = nodes P
+// Three products live here: (1) the NN product of the forward and the data gradient (Geo, pack,
+// gemm_nn_split_body); (2) the NT product of the weight gradient with both operands split in the kernel
+// (gemm_nt_split_w4_mf16 on split_nt.hpp's gemm_nt_split_body, split-K summed by split_sum_nt); (3) the
+// same with dy split once beforehand (split_rows, gemm_nt_psa on split_nt.hpp's PsaBody, row_sums).  The
+// edge encoder's backward builds its kernels from the same NT bodies in encoder_bwd_split.hip.
+//
+// The NN product is the same as compress_gemm.hip's gemm_nn (which runs it on the fp32 MFMA), here on
 // v_mfma_f32_32x32x16_bf16 with the exact three-way bf16 split of encoder_split.hip: every fp32 operand
 // x = x0 + x1 + x2 (+ < 2^-24 |x|), each product the sum of the six partial products a_i b_j with
 // i + j <= 2, exact in the MFMA and summed in fp32 — as accurate as an fp32 GEMM (the omitted terms are
@@ -34,29 +41,20 @@
 // Part count.  Every kernel of the compress takes a compile-time NP = 3 / 2 / 1: the bf16 parts kept per
 // operand, with the partial products i + j < NP (six, three, one).  The reduced forms skip the dropped
 // parts' conversions, LDS stores, fragment reads, weight-image pieces and MFMAs (mrp_compress_*_split_p;
-// DESIGN.md §3.11); the numbers above are NP = 3's.  The encoder's kernels here stay at NP = 3.
+// DESIGN.md §3.11); the numbers above are NP = 3's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-#include <functional>
-#include <map>
-#include <mutex>
-#include <vector>
-
 #include "gemm_common.hpp"
 #include "mrp_gnn.h"
 #include "split_common.hpp"
+#include "split_nt.hpp"
 #include "tuning.hpp"
 
 namespace mrp_cs {
 
-// vector types, rsrc, xcd_remap, tile_of, the LDS image offsets boff / rowoff: gemm_common.hpp; the bf16
-// split (split2 / splitp), the partial products (mma6 / mma6_16) and the counted waits: split_common.hpp
-using namespace mrp_gemm;
-
-constexpr int TN = 128, BK = 32;
+// TN, BK, the NT product's NTArgs / NTGeo and bodies, `using namespace mrp_gemm`: split_nt.hpp
 constexpr int B_PART_BYTES = BK * TN * 2;  // one bf16 part of the B stage: 8 KiB
 
 // Workgroup geometry: WMW x 2 waves of 64 x 64, TM = 64 WMW rows; NP = the bf16 parts kept per operand
@@ -439,19 +437,14 @@ __global__ void __launch_bounds__(512, 1) gemm_nn_split_w4_mf16(Args a) {
   gemm_nn_split_body<4, true, NP>(a);
 }
 
-// one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
 template <int WMW, int NP, void (*K)(Args)>
 hipError_t launch_w(Args a, hipStream_t st) {
   using G = Geo<WMW, NP>;
   a.mtiles = (a.M + G::TM - 1) / G::TM;
   const int64_t grid = (int64_t)a.mtiles * ((a.ncols + TN - 1) / TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
   a.group = mrp_host::tuning().gemm_group;
-  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-  return hipGetLastError();
+  return launch_lds<K>(G::LDS_BYTES, dim3((unsigned)grid), dim3(G::THREADS), st, a);
 }
 
 // the 16x16x32 form's epilogue: 16-row blocks on one side of m0, 32-bit buffer offsets into c0 / c1
@@ -480,191 +473,10 @@ hipError_t launch(Args a, hipStream_t st) {
   return launch_w<2, NP, gemm_nn_split_w2<NP>>(a, st);
 }
 
-// parts (validated by the caller) -> the instantiation
-hipError_t launch_parts(const Args& a, int parts, hipStream_t st) {
-  return parts == 3 ? launch<3>(a, st) : parts == 2 ? launch<2>(a, st) : launch<1>(a, st);
-}
-
 // ------------------------------------------------------------------------------------------------
-// Weight gradient  dW[m][n] = sum_k dy[m][k] S[n][k],  db[m] = sum_k dy[m][k],  k = (node, pixel):
-// both operands are k-contiguous rows (a channel's P pixels of one node), so no transposing read is
-// needed — each thread loads 16-byte row pieces of a stage (A = dy: TMW rows, B = [x; agg]: 128 rows,
-// 32 pixels of one node), splits them and stores the three bf16 parts as [row][32 k] 64-byte rows (the
-// row's four 16-byte chunks rotated by (row >> 2) & 3, so the fragment reads meet every bank once),
-// from which a lane's eight consecutive k are one ds_read_b128.  K = Nt P is split over workgroups
-// (whole stages, each within one node) into per-split partial tiles summed in a fixed order by
-// split_sum_nt (deterministic); db from the fp32 dy pieces as loaded, per split.
+// Weight gradient  dW = dy [x; agg]^T, db = the row sums of dy: the NT product of split_nt.hpp, whose
+// bodies these kernels and the edge encoder's backward (encoder_bwd_split.hip) instantiate.
 // ------------------------------------------------------------------------------------------------
-struct NTArgs {
-  const float* g;  // dy (nodes, M, P), node stride gs
-  int64_t gs;
-  const float* s0;  // rows [0, n0) of B: x (nodes, n0, P)
-  int64_t s0s;
-  const float* s1;  // rows [n0, N): agg
-  int64_t s1s;
-  float* out;   // [split][M][N]
-  float* outb;  // [split][M] or null
-  int64_t ktot, kchunk;
-  int32_t M, N, n0, P, mtiles, ntiles;
-  const u4* ap;  // gemm_nt_psa: the pre-split image of g (split_rows), KS = ktot / 16 16-k steps per row block
-  int32_t group;  // tile order (tile_of)
-};
-
-template <int WMW, int NP = 3>
-struct NTGeo {
-  static constexpr int TM = 64 * WMW, NW = 2 * WMW, THREADS = 64 * NW;
-  static constexpr int ROWB = BK * 2;                                  // bytes per [row][32 k] bf16 row
-  static constexpr int A_PART = TM * ROWB, B_PART = TN * ROWB;
-  static constexpr int BUF_BYTES = NP * (A_PART + B_PART);
-  static constexpr int LDS_BYTES = 2 * BUF_BYTES;                      // 144 KiB at WMW 4, NP 3 (x NP / 3)
-  static constexpr int RPP = THREADS / 8;                              // rows per load pass (8 pieces a row)
-  static constexpr int AJ = TM / RPP, BJ = TN / RPP;                   // A / B pieces per thread per stage
-};
-
-// The products on v_mfma_f32_16x16x32_bf16 (the wave's 64 x 64 as 4 x 4 tiles of 16 x 16, one MFMA per
-// 32 k), which holds a higher clock than the 32x32x16 shape under the chip's power limit
-// (MI355X_MICROARCH.md, DVFS give-back item 7); the 32x32x16 forms are lab forms (tools/lab_forms.hip)
-template <int WMW, int NP = 3>
-__device__ __forceinline__ void gemm_nt_split_body(const NTArgs& a, int orig, int nwg) {
-  using G = NTGeo<WMW, NP>;
-  extern __shared__ u4 lds[];
-  char* ldsb = reinterpret_cast<char*>(lds);
-  const int id = xcd_remap(orig, nwg);
-  const int tiles = a.mtiles * a.ntiles;
-  const int split = id / tiles, tid = id - split * tiles;
-  int mt, nt;
-  tile_of(tid, a.mtiles, a.ntiles, a.group, mt, nt);
-  const int mbase = mt * G::TM, nbase = nt * TN;
-  const int64_t kbeg = (int64_t)split * a.kchunk;
-  const int64_t kend = kbeg + a.kchunk < a.ktot ? kbeg + a.kchunk : a.ktot;
-  const int nst = kend > kbeg ? (int)((kend - kbeg) / BK) : 0;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = w >> 1, wn = w & 1;
-
-  // ---- loads: thread t -> piece (t & 7) (4 pixels) of rows (t >> 3) + RPP j
-  const int pc4 = threadIdx.x & 7, r0 = threadIdx.x >> 3;
-  int64_t aoff[G::AJ], boffs[G::BJ];  // row offsets within a node (elements), fixed
-  bool bhi[G::BJ];
-#pragma unroll
-  for (int j = 0; j < G::AJ; ++j) aoff[j] = (int64_t)min(mbase + r0 + G::RPP * j, a.M - 1) * a.P + 4 * pc4;
-#pragma unroll
-  for (int j = 0; j < G::BJ; ++j) {
-    const int n = min(nbase + r0 + G::RPP * j, a.N - 1);
-    bhi[j] = n >= a.n0;
-    boffs[j] = (int64_t)(bhi[j] ? n - a.n0 : n) * a.P + 4 * pc4;
-  }
-  f4 areg[G::AJ], breg[G::BJ];
-  float rsum[G::AJ];
-#pragma unroll
-  for (int j = 0; j < G::AJ; ++j) rsum[j] = 0.f;
-  // stages in order, k = (node ind, pixel ipx) advanced per stage (P % BK == 0: a stage never straddles
-  // two nodes) — an int64 division per stage put ~80 scalar instructions between the barrier and the
-  // stage's loads
-  int64_t ind = kbeg / a.P;
-  int ipx = (int)(kbeg - ind * a.P);
-  auto load = [&]() {
-    const float* gp = a.g + ind * a.gs + ipx;
-    const float* xp = a.s0 + ind * a.s0s + ipx;
-    const float* ap = a.s1 + ind * a.s1s + ipx;
-#pragma unroll
-    for (int j = 0; j < G::AJ; ++j) areg[j] = *reinterpret_cast<const f4*>(gp + aoff[j]);
-#pragma unroll
-    for (int j = 0; j < G::BJ; ++j) breg[j] = *reinterpret_cast<const f4*>((bhi[j] ? ap : xp) + boffs[j]);
-    ipx += BK;
-    if (ipx == a.P) {
-      ipx = 0;
-      ++ind;
-    }
-  };
-  auto store = [&](int buf) {
-    char* base = ldsb + buf * G::BUF_BYTES;
-    auto put = [&](char* img, int part_bytes, int row, const f4& v) {
-      f2 lo, hi;
-      lo.x = v.x, lo.y = v.y, hi.x = v.z, hi.y = v.w;
-      uint32_t l[NP], h[NP];
-      splitp<NP>(lo, l);
-      splitp<NP>(hi, h);
-      const uint32_t o = rowoff(row, pc4 >> 1) + 8 * (pc4 & 1);
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        u2 u;
-        u.x = l[p], u.y = h[p];
-        *reinterpret_cast<u2*>(img + p * part_bytes + o) = u;
-      }
-    };
-#pragma unroll
-    for (int j = 0; j < G::AJ; ++j) {
-      rsum[j] += (areg[j].x + areg[j].y) + (areg[j].z + areg[j].w);
-      put(base, G::A_PART, r0 + G::RPP * j, areg[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < G::BJ; ++j) put(base + NP * G::A_PART, G::B_PART, r0 + G::RPP * j, breg[j]);
-  };
-  // lane (r16, q) reads k = 8 q .. 8 q + 7 (chunk q) of row r16 of a 16-row block
-  const int r16 = lane & 15, q = lane >> 4;
-  Acc2s acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[mi][ni].hi[r] = acc[mi][ni].lo[r] = 0.f;
-  if (nst > 0) load();
-#pragma unroll 1
-  for (int s = 0; s < nst; ++s) {
-    const int buf = s & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    store(buf);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (s + 1 < nst) load();
-    const char* base = ldsb + buf * G::BUF_BYTES;
-    const char* bb = base + NP * G::A_PART;
-    bf8 bf[4][NP];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-        bf[ni][p] = __builtin_bit_cast(bf8, *reinterpret_cast<const u4*>(bb + p * G::B_PART +
-                                                                          rowoff(64 * wn + 16 * ni + r16, q)));
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      bf8 af[NP];
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-        af[p] = __builtin_bit_cast(bf8, *reinterpret_cast<const u4*>(base + p * G::A_PART +
-                                                                      rowoff(64 * wm + 16 * mi + r16, q)));
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) mma6_16<NP>(af, bf[ni], acc[mi][ni]);
-    }
-  }
-  float* out = a.out + (int64_t)split * a.M * a.N;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = nbase + 64 * wn + 16 * ni + r16;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = mbase + 64 * wm + 16 * mi + 4 * q + r;
-        if (m < a.M) out[(int64_t)m * a.N + n] = __fadd_rn(acc[mi][ni].hi[r], acc[mi][ni].lo[r]);
-      }
-  }
-  if (a.outb != nullptr && nt == 0) {  // the column-tile-0 workgroups write the split's row sums
-#pragma unroll
-    for (int j = 0; j < G::AJ; ++j) {
-      float v = rsum[j];  // the 8 threads of a row are 8 consecutive lanes (t & 7)
-      v += __shfl_xor(v, 1, 64);
-      v += __shfl_xor(v, 2, 64);
-      v += __shfl_xor(v, 4, 64);
-      const int m = mbase + r0 + G::RPP * j;
-      if (pc4 == 0 && m < a.M) a.outb[(int64_t)split * a.M + m] = v;
-    }
-  }
-}
-
 template <int NP>
 __global__ void __launch_bounds__(512, 1) gemm_nt_split_w4_mf16(NTArgs a) {
   gemm_nt_split_body<4, NP>(a, blockIdx.x, gridDim.x);
@@ -749,229 +561,9 @@ __global__ void __launch_bounds__(64) row_sums(const float* __restrict__ part, i
   if (lane == 0) out[m] = v;
 }
 
-// NP: the parts kept of both operands; the image at a.ap holds NP parts per (block, step) (split_rows<NP>;
-// NP 3: `pack`'s layout)
-// (a static member of a class template, reached through the function template below: hipcc's host pass
-// drops a function template's specialization with these inline-asm immediates when a non-template
-// kernel names it — gemm_nt_psa<3>'s host stub went with it)
-template <int NP>
-struct PsaBody {
-static __device__ __forceinline__ void run(const NTArgs& a, int orig, int nwg) {
-  using G = NTGeo<4, NP>;
-  constexpr int A_BYTES = 16 * NP * 1024;  // 256 rows x 32 k x NP parts: 16 NP 1-KiB pieces, 2 NP per wave
-  constexpr int BP = G::B_PART, BUF = A_BYTES + NP * BP;  // NP 3: 72 KiB per buffer, two buffers
-  extern __shared__ u4 lds[];
-  char* ldsb = reinterpret_cast<char*>(lds);
-  const int id = xcd_remap(orig, nwg);
-  const int tiles = a.mtiles * a.ntiles;
-  const int split = id / tiles, tid = id - split * tiles;
-  int mt, nt;
-  tile_of(tid, a.mtiles, a.ntiles, a.group, mt, nt);
-  const int mbase = mt * G::TM, nbase = nt * TN;
-  const int64_t kbeg = (int64_t)split * a.kchunk;
-  const int64_t kend = kbeg + a.kchunk < a.ktot ? kbeg + a.kchunk : a.ktot;
-  const int nst = kend > kbeg ? (int)((kend - kbeg) / BK) : 0;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int64_t KS = a.ktot / 16;
-  const int MB = a.M / 32;
-
-  // ---- A: LDS-DMA pieces pc = (mbl 2 + ksl) NP + p of the stage, pc = w + 8 i
-  const __amdgpu_buffer_rsrc_t ra = rsrc(a.ap);
-  uint32_t va[2 * NP];
-#pragma unroll
-  for (int i = 0; i < 2 * NP; ++i) {
-    const int pc = w + 8 * i;
-    const int mbl = pc / (2 * NP), kp = pc % (2 * NP);  // kp = NP ksl + p
-    const int mb = min(mt * 8 + mbl, MB - 1);  // blocks past M: any valid data, never stored
-    va[i] = (uint32_t)((((int64_t)mb * KS + kbeg / 16) * NP + kp) * 64 + lane) * 16;
-  }
-  auto issue_a = [&](int s, int buf) {
-#pragma unroll
-    for (int i = 0; i < 2 * NP; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, lds + (buf * BUF + (w + 8 * i) * 1024) / 16, 16, va[i],
-                                               (uint32_t)s * 2 * NP * 1024, 0, 0);
-  };
-
-  // ---- B: thread t -> piece (t & 7) (4 pixels) of rows (t >> 3) + 64 j of the stage
-  const int pc4 = threadIdx.x & 7, r0 = threadIdx.x >> 3;
-  int64_t boffs[G::BJ];
-  bool bhi[G::BJ];
-#pragma unroll
-  for (int j = 0; j < G::BJ; ++j) {
-    const int n = min(nbase + r0 + G::RPP * j, a.N - 1);
-    bhi[j] = n >= a.n0;
-    boffs[j] = (int64_t)(bhi[j] ? n - a.n0 : n) * a.P + 4 * pc4;
-  }
-  f4 breg[G::BJ];
-  int64_t ind = kbeg / a.P;
-  int ipx = (int)(kbeg - ind * a.P);
-  auto load_b = [&]() {
-    const float* xp = a.s0 + ind * a.s0s + ipx;
-    const float* ap = a.s1 + ind * a.s1s + ipx;
-#pragma unroll
-    for (int j = 0; j < G::BJ; ++j) breg[j] = *reinterpret_cast<const f4*>((bhi[j] ? ap : xp) + boffs[j]);
-    ipx += BK;
-    if (ipx == a.P) {
-      ipx = 0;
-      ++ind;
-    }
-  };
-  auto store_b = [&](int buf) {
-    char* img = ldsb + buf * BUF + A_BYTES;
-#pragma unroll
-    for (int j = 0; j < G::BJ; ++j) {
-      f2 lo, hi;
-      lo.x = breg[j].x, lo.y = breg[j].y, hi.x = breg[j].z, hi.y = breg[j].w;
-      uint32_t l[NP], h[NP];
-      splitp<NP>(lo, l);
-      splitp<NP>(hi, h);
-      const uint32_t o = rowoff(r0 + G::RPP * j, pc4 >> 1) + 8 * (pc4 & 1);
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        u2 u;
-        u.x = l[p], u.y = h[p];
-        *reinterpret_cast<u2*>(img + p * BP + o) = u;
-      }
-    }
-  };
-
-  // fragments: lane (r16, qq) holds k = 8 qq .. 8 qq + 7 of row r16 of a 16-row block.  A: 16-row block mi
-  // of the wave is half (mi & 1) of 32-row block 2 wm + (mi >> 1); the packed image holds 16-k steps in the
-  // 32 x 32 x 16 lane order, so the lane reads step qq >> 1, slot 16 (mi & 1) + r16 + 32 (qq & 1) (the NN
-  // kernel's A reads).  B: chunk qq of row 64 wn + 16 ni + r16 of the [row][32 k] images.
-  const int r16 = lane & 15, qq = lane >> 4;
-  const uint32_t abase0 = (uint32_t)reinterpret_cast<uintptr_t>(ldsb + (r16 + 32 * (qq & 1)) * 16 +
-                                                                 ((4 * wm + (qq >> 1)) * NP) * 1024);
-  uint32_t bro[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni)
-    bro[ni] = (uint32_t)reinterpret_cast<uintptr_t>(ldsb + A_BYTES + rowoff(64 * wn + 16 * ni + r16, qq));
-  Acc2s acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[mi][ni].hi[r] = acc[mi][ni].lo[r] = 0.f;
-  if (nst > 0) {
-    issue_a(0, 0);
-    load_b();
-  }
-#pragma unroll 1
-  for (int s = 0; s < nst; ++s) {
-    const int buf = s & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stage s's B registers and own A pieces landed
-    store_b(buf);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // stage s complete for every wave; every wave is past stage s - 1's reads
-    {
-      // every fragment read by inline asm with counted waits (a C++ LDS read beside the LDS-DMA issued
-      // below would make hipcc wait for the DMA): A row 0, B columns 0..3, then A row mi + 1 under row
-      // mi's MFMAs
-      const uint32_t ab = abase0 + (uint32_t)(buf * BUF);
-      u4 ar[2][NP], br[4][NP];
-      auto read_a16 = [&](int mi, u4 (&rg)[NP]) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-          asm volatile("ds_read_b128 %0, %1 offset:%2"
-                       : "=v"(rg[p])
-                       : "v"(ab), "i"((mi >> 1) * 2048 * NP + p * 1024 + 256 * (mi & 1)));
-      };
-      read_a16(0, ar[0]);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-          asm volatile("ds_read_b128 %0, %1 offset:%2"
-                       : "=v"(br[ni][p])
-                       : "v"(bro[ni] + (uint32_t)(buf * BUF)), "i"(p * BP));
-      if (s + 1 < nst) {
-        issue_a(s + 1, buf ^ 1);
-        load_b();
-      }
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        u4 (&cur)[NP] = ar[mi & 1];
-        if (mi < 3) read_a16(mi + 1, ar[(mi + 1) & 1]);
-        if (mi > 0) {
-          if (mi < 3)
-            wait_lgkm<NP>();  // row mi + 1's reads stay in flight
-          else
-            wait_lgkm<0>();
-          pin<NP>(cur);
-        }
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          if (mi == 0) {
-            // A row 0 and B columns 0..ni landed: younger are NP (3 - ni) B reads and A row 1's NP
-            // (NP 3: 12, 9, 6, 3)
-            if (ni == 0)
-              wait_lgkm<4 * NP>();
-            else if (ni == 1)
-              wait_lgkm<3 * NP>();
-            else if (ni == 2)
-              wait_lgkm<2 * NP>();
-            else
-              wait_lgkm<NP>();
-            if (ni == 0) pin<NP>(cur);
-            pin<NP>(br[ni]);
-          }
-          bf8 af[NP], bfr[NP];
-#pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            af[p] = __builtin_bit_cast(bf8, cur[p]);
-            bfr[p] = __builtin_bit_cast(bf8, br[ni][p]);
-          }
-          mma6_16<NP>(af, bfr, acc[mi][ni]);
-          if (mi == 0 || ni == 3) __builtin_amdgcn_sched_barrier(0);  // keep each wait before its MFMAs
-        }
-      }
-    }
-  }
-  float* out = a.out + (int64_t)split * a.M * a.N;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = nbase + 64 * wn + 16 * ni + r16;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = mbase + 64 * wm + 16 * mi + 4 * qq + r;
-        if (m < a.M) out[(int64_t)m * a.N + n] = __fadd_rn(acc[mi][ni].hi[r], acc[mi][ni].lo[r]);
-      }
-  }
-}
-};
-template <int NP>
-__device__ __forceinline__ void gemm_nt_psa_body(const NTArgs& a, int orig, int nwg) {
-  PsaBody<NP>::run(a, orig, nwg);
-}
-
 template <int NP>
 __global__ void __launch_bounds__(512, 1) gemm_nt_psa(NTArgs a) {
   gemm_nt_psa_body<NP>(a, blockIdx.x, gridDim.x);
-}
-
-// the same with the first product's A operand pre-split (gemm_nt_psa_body: the edge encoder's W2^T,
-// packed once per weight version) — the split body re-split it once per column tile and call
-// (the encoder's kernels keep all three parts)
-__global__ void __launch_bounds__(512, 1) gemm_nt_dual_psa1(NTArgs a1, NTArgs a2, int grid1) {
-  if ((int)blockIdx.x < grid1)
-    gemm_nt_psa_body<3>(a1, blockIdx.x, grid1);
-  else
-    gemm_nt_split_body<4>(a2, blockIdx.x - grid1, gridDim.x - grid1);
-}
-
-// two independent NT products in one launch (the edge encoder's backward), on the default (16x16x32)
-// form: workgroups [0, grid1) run a1, the rest a2, each product with its own XCD-aware tile order
-__global__ void __launch_bounds__(512, 1) gemm_nt_dual_mf16(NTArgs a1, NTArgs a2, int grid1) {
-  if ((int)blockIdx.x < grid1)
-    gemm_nt_split_body<4>(a1, blockIdx.x, grid1);
-  else
-    gemm_nt_split_body<4>(a2, blockIdx.x - grid1, gridDim.x - grid1);
 }
 
 // out = sum over the splits of part (fixed order); outb = the same over nsplitb row-sum partials
@@ -1074,7 +666,7 @@ extern "C" int mrp_compress_fwd_split_p(const float* x, int64_t x_node_stride, c
   a.k0 = C;
   a.m0 = C;
   a.P = P;
-  return launch_parts(a, parts, static_cast<hipStream_t>(stream));
+  return dispatch_parts(parts, [&](auto np) { return launch<decltype(np)::value>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int mrp_compress_fwd_split(const float* x, int64_t x_node_stride, const float* agg, int64_t agg_node_stride,
@@ -1113,7 +705,7 @@ extern "C" int mrp_compress_bwd_data_split_p(const float* gy, int64_t gy_node_st
   a.k0 = C;
   a.m0 = C;
   a.P = P;
-  return launch_parts(a, parts, static_cast<hipStream_t>(stream));
+  return dispatch_parts(parts, [&](auto np) { return launch<decltype(np)::value>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int mrp_compress_bwd_data_split(const float* gy, int64_t gy_node_stride, int32_t num_nodes, int32_t C,
@@ -1123,43 +715,15 @@ extern "C" int mrp_compress_bwd_data_split(const float* gy, int64_t gy_node_stri
                                        gagg_node_stride, 3, stream);
 }
 
-namespace {
-bool nt_split_ok(int32_t num_nodes, int32_t C, int32_t P) {
-  return num_nodes > 0 && C > 0 && C % 64 == 0 && P % BK == 0;
-}
-
-// workspace bytes of one NT product (split-K partial tiles, and row sums when wanted)
-int64_t nt_workspace(int64_t M, int64_t N, int64_t ktot) {
+// (the two host functions split_nt.hpp declares: encoder_bwd_split.hip calls them too)
+int64_t mrp_cs::nt_workspace(int64_t M, int64_t N, int64_t ktot) {
   const int64_t tiles = ((M + NTGeo<4>::TM - 1) / NTGeo<4>::TM) * ((N + TN - 1) / TN);
   int64_t kchunk;
   return splitk_place(nt_splits(tiles, ktot, M, N, &kchunk), M, N).bytes;
 }
 
-// one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
-template <int NP>
-hipError_t launch_nt(const NTArgs& a, int64_t grid, hipStream_t st) {
-  using G = NTGeo<4, NP>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_w4_mf16<NP>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_nt_split_w4_mf16<NP>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-  return hipGetLastError();
-}
-
-template <int NP>
-hipError_t launch_psa(const NTArgs& a, int64_t grid, hipStream_t st) {
-  using G = NTGeo<4, NP>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_psa<NP>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_nt_psa<NP>, dim3((unsigned)grid), dim3(G::THREADS), G::LDS_BYTES, st, a);
-  return hipGetLastError();
-}
-
-// out (M x N) = sum_k g[m][k] s[n][k] (+ row sums of g into outb), k = (node, pixel) over `nodes` nodes of
-// P pixels; a.g/gs, a.s0/s0s, a.s1/s1s, a.n0, a.P set by the caller; parts = the bf16 parts kept (1..3)
-hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, float* outb, void* workspace,
-                  int64_t workspace_bytes, hipStream_t st, int parts = 3) {
+hipError_t mrp_cs::nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, float* outb, void* workspace,
+                          int64_t workspace_bytes, hipStream_t st, int parts) {
   using G = NTGeo<4>;
   a.mtiles = (int32_t)((M + G::TM - 1) / G::TM);
   a.ntiles = (int32_t)((N + TN - 1) / TN);
@@ -1177,9 +741,17 @@ hipError_t nt_run(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out, flo
   // instead at 4, and at -1 where C >= 1024).  Round 4's 32x32x16 forms (the 32-k-stage one and the
   // pipelined 16-k-stage one), 4-5 % slower at every config shape, are lab forms (tools/lab_forms.hip).
   a.group = mrp_host::tuning().nt_group;
-  hipError_t e = parts == 3 ? launch_nt<3>(a, grid, st) : parts == 2 ? launch_nt<2>(a, grid, st) : launch_nt<1>(a, grid, st);
+  const hipError_t e = dispatch_parts(parts, [&](auto np) {
+    constexpr int NP = decltype(np)::value;
+    return launch_lds<gemm_nt_split_w4_mf16<NP>>(NTGeo<4, NP>::LDS_BYTES, dim3((unsigned)grid), dim3(G::THREADS), st, a);
+  });
   if (e != hipSuccess || ns == 1) return e;
   return split_sum(pl.out, ns, M, N, out, pl.outb, ns, outb, st);
+}
+
+namespace {
+bool nt_split_ok(int32_t num_nodes, int32_t C, int32_t P) {
+  return num_nodes > 0 && C > 0 && C % 64 == 0 && P % BK == 0;
 }
 
 // The pre-split-A weight gradient (split_rows + gemm_nt_psa): workspace = [partial tiles (splits > 1)]
@@ -1218,8 +790,7 @@ PsaPlan psa_plan(int64_t M, int64_t N, int64_t ktot) {
 }
 
 // The pre-split-A GEMM proper: dW (+ db from rparts row-sum partials [M][nparts]) from dy's packed
-// image `img` (split_rows' layout, or written by the data gradient: mrp_compress_bwd_data_split_img);
-// the workspace holds the partial tiles when the plan splits K
+// image `img` (split_rows' layout); the workspace holds the partial tiles when the plan splits K
 hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* rparts, int nparts, float* out,
                     float* outb, void* tiles_ws, hipStream_t st, int parts) {
   using G = NTGeo<4>;
@@ -1235,7 +806,10 @@ hipError_t psa_gemm(NTArgs a, int64_t M, int64_t N, const u4* img, const float* 
   const int64_t grid = (int64_t)a.mtiles * a.ntiles * q.ns;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   a.group = mrp_host::tuning().nt_group;
-  hipError_t e = parts == 3 ? launch_psa<3>(a, grid, st) : parts == 2 ? launch_psa<2>(a, grid, st) : launch_psa<1>(a, grid, st);
+  hipError_t e = dispatch_parts(parts, [&](auto np) {
+    constexpr int NP = decltype(np)::value;
+    return launch_lds<gemm_nt_psa<NP>>(NTGeo<4, NP>::LDS_BYTES, dim3((unsigned)grid), dim3(G::THREADS), st, a);
+  });
   if (e != hipSuccess) return e;
   if (outb != nullptr) {
     hipLaunchKernelGGL(row_sums, dim3((unsigned)M), dim3(64), 0, st, rparts, nparts, (int32_t)M, outb);
@@ -1258,15 +832,10 @@ hipError_t nt_run_psa(NTArgs a, int64_t M, int64_t N, int32_t nodes, float* out,
   const int64_t waves = (M / 32) * q.ngroups;
   const dim3 sgrid((unsigned)((waves + 3) / 4));
   float* rsp = outb != nullptr ? rs : nullptr;
-  if (parts == 3)
-    hipLaunchKernelGGL(split_rows<3>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
-                       img, rsp);
-  else if (parts == 2)
-    hipLaunchKernelGGL(split_rows<2>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
-                       img, rsp);
-  else
-    hipLaunchKernelGGL(split_rows<1>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P, a.ktot / 16, q.G, q.ngroups,
-                       img, rsp);
+  dispatch_parts(parts, [&](auto np) {
+    hipLaunchKernelGGL(split_rows<decltype(np)::value>, sgrid, dim3(256), 0, st, a.g, a.gs, (int32_t)M, a.P,
+                       a.ktot / 16, q.G, q.ngroups, img, rsp);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return psa_gemm(a, M, N, img, rs, q.ngroups, out, outb, ws, st, parts);
@@ -1323,414 +892,4 @@ extern "C" int mrp_compress_bwd_weight_split(const float* gy, int64_t gy_node_st
                                              void* workspace, int64_t workspace_bytes, void* stream) {
   return mrp_compress_bwd_weight_split_p(gy, gy_node_stride, x, x_node_stride, agg, agg_node_stride, num_nodes, C, P,
                                          gw, gbias, workspace, workspace_bytes, 3, stream);
-}
-
-// The edge encoder's backward GEMMs on the same kernel (training path, encoder.py): operands are rows
-// with k contiguous, i.e. one "node" of K pixels:
-//   dh^T (C x E)  = W2^T (C x 2C) . dz^T     (k = j: rows of W2^T and of dz)
-//   dW2 (2C x C)  = dz^T (2C x E) . h         (k = e: rows of dz^T and of h^T; db2 = its row sums of dz^T)
-extern "C" int64_t mrp_edge_encoder_bwd_split_workspace(int32_t num_edges, int32_t C) {
-  if (num_edges <= 0 || C <= 0 || num_edges % BK != 0 || C % 32 != 0) return 0;
-  const int64_t a = nt_workspace(C, num_edges, 2 * (int64_t)C), b = nt_workspace(2 * (int64_t)C, C, num_edges);
-  return a > b ? a : b;
-}
-
-extern "C" int mrp_edge_encoder_bwd_split(const float* dz, const float* dzT, const float* w2T, const float* hT,
-                                          int32_t num_edges, int32_t C, float* dhT, float* dw2, float* db2,
-                                          void* workspace, int64_t workspace_bytes, void* stream) {
-  if (num_edges < 0 || C < 0) return hipErrorInvalidValue;
-  if (db2 != nullptr && dw2 == nullptr) return hipErrorInvalidValue;  // db2 rides on the dW2 product
-  if (num_edges == 0 || C == 0 || (dhT == nullptr && dw2 == nullptr)) return hipSuccess;
-  if (num_edges % BK != 0 || C % 32 != 0) return hipErrorNotSupported;
-  if ((dhT && (!dz || !w2T || !aligned16(dz) || !aligned16(w2T) || !aligned16(dhT))) ||
-      (dw2 && (!dzT || !hT || !aligned16(dzT) || !aligned16(hT) || !aligned16(dw2))))
-    return hipErrorInvalidValue;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t E = num_edges, C2 = 2 * (int64_t)C;
-  if (dhT) {
-    NTArgs a = {};
-    a.g = w2T;  // rows u, k = j
-    a.gs = C * C2;
-    a.s0 = dz;  // rows e, k = j
-    a.s0s = E * C2;
-    a.s1 = dz;
-    a.s1s = E * C2;
-    a.n0 = (int32_t)E;
-    a.P = (int32_t)C2;
-    const hipError_t e = nt_run(a, C, E, 1, dhT, nullptr, workspace, workspace_bytes, st);
-    if (e != hipSuccess) return e;
-  }
-  if (dw2) {
-    NTArgs a = {};
-    a.g = dzT;  // rows j, k = e
-    a.gs = C2 * E;
-    a.s0 = hT;  // rows u, k = e
-    a.s0s = (int64_t)C * E;
-    a.s1 = hT;
-    a.s1s = (int64_t)C * E;
-    a.n0 = C;
-    a.P = (int32_t)E;
-    return nt_run(a, C2, C, 1, dw2, db2, workspace, workspace_bytes, st);  // row sums of dz^T = db2
-  }
-  return hipSuccess;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The edge encoder's whole backward in three launches on one stream (training path, encoder.py):
-//   1. dz^T                                     (mrp_edge_encoder_bwd_prep)
-//   2. dh^T = W2^T dz^T and dW2 = dz^T h        one launch of both split-K NT products, splits chosen
-//                                               jointly so the two fill one round of the chip
-//   3. encoder_bwd_reduce: dW2 and db2 = the fixed-order sums of their partial tiles / row sums; and,
-//      per hidden unit (one workgroup over all edges), dh^T summed from its partial tiles, masked by
-//      [h^T > 0] (ReLU) and reduced against the pose rows into dW1 / db1 — dh^T never written.
-//      (Round 4 first reduced per (4 units, 256 edges) into partials summed by a fourth launch: the
-//      whole backward 46.2 -> 42.8 us at E = 1792, C = 512, tools/exp_enc_bwd.py.)
-// ------------------------------------------------------------------------------------------------
-namespace mrp_cs {
-
-constexpr int kNin = 9;
-
-// dz (E x N2, row-major) -> the packed split image of dz^T (N2 x E, k = the edges; `pack`'s layout, the
-// dW2 product's A operand, read by LDS-DMA) and db2's partials csum[eb][j] = sum of dz[e][j] over the
-// 64-edge block eb in edge order (summed over the blocks in order by encoder_bwd_reduce).  64 x 64 tile
-// through LDS as dz_transpose; lane -> (row j0 + (u & 63), edges 8 (u >> 6) ..): a wave's 32-row halves
-// store 512 contiguous bytes per part.  E % 16 == 0.
-__global__ void __launch_bounds__(256) dzT_pack(const float* __restrict__ dz, int E, int N2, u4* __restrict__ img,
-                                                float* __restrict__ csum) {
-  __shared__ float tile[64][65];
-  const int j0 = blockIdx.x * 64, e0 = blockIdx.y * 64;
-  const int c4 = threadIdx.x & 15, r0 = threadIdx.x >> 4;
-  f4 v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int e = e0 + r0 + 16 * i, j = j0 + 4 * c4;
-    v[i] = (e < E && j < N2) ? *reinterpret_cast<const f4*>(dz + (int64_t)e * N2 + j) : f4{0.f, 0.f, 0.f, 0.f};
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tile[r0 + 16 * i][4 * c4 + q] = v[i][q];
-  __syncthreads();
-  if (threadIdx.x < 64 && j0 + (int)threadIdx.x < N2) {
-    float sum = 0.f;
-    for (int e = 0; e < 64; ++e) sum += tile[e][threadIdx.x];
-    csum[(int64_t)blockIdx.y * N2 + j0 + threadIdx.x] = sum;
-  }
-  const int64_t KS = E / 16;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int u = threadIdx.x + 256 * i;
-    const int jl = u & 63, g8 = u >> 6;
-    const int j = j0 + jl, e = e0 + 8 * g8;
-    if (j >= N2 || e >= E) continue;
-    u4 p0, p1, p2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f2 x;
-      x.x = tile[8 * g8 + 2 * q][jl];
-      x.y = tile[8 * g8 + 2 * q + 1][jl];
-      uint32_t a0, a1, a2;
-      split2(x, a0, a1, a2);
-      p0[q] = a0, p1[q] = a1, p2[q] = a2;
-    }
-    const int64_t base = (((int64_t)(j >> 5) * KS + (e >> 4)) * 3) * 64 + (j & 31) + 32 * ((e >> 3) & 1);
-    img[base] = p0;
-    img[base + 64] = p1;
-    img[base + 128] = p2;
-  }
-}
-
-// both products with a pre-split A: W2^T's packed image and dz^T's (dzT_pack)
-__global__ void __launch_bounds__(512, 1) gemm_nt_dual_psa2(NTArgs a1, NTArgs a2, int grid1) {
-  if ((int)blockIdx.x < grid1)
-    gemm_nt_psa_body<3>(a1, blockIdx.x, grid1);
-  else
-    gemm_nt_psa_body<3>(a2, blockIdx.x - grid1, gridDim.x - grid1);
-}
-
-struct EncPlan {
-  int s1, s2;
-  int64_t kc1, kc2;
-  int t1, t2;  // tiles of each product
-  int64_t off_dzT, off_p1, off_p2, off_p2b, bytes;
-};
-
-EncPlan enc_plan(int64_t E, int64_t C) {
-  EncPlan pl{};
-  const int64_t C2 = 2 * C;
-  pl.t1 = (int)(((C + NTGeo<4>::TM - 1) / NTGeo<4>::TM) * ((E + TN - 1) / TN));       // dh^T: M = C, N = E
-  pl.t2 = (int)(((C2 + NTGeo<4>::TM - 1) / NTGeo<4>::TM) * ((C + TN - 1) / TN));      // dW2: M = 2C, N = C
-  const int64_t st1 = C2 / BK, st2 = E / BK;                                // 32-k split granules
-  // Split counts: the makespan of the launch's workgroups dispatched in order (the a t1 units of the
-  // first product, p1 stages each, then the b t2 of the second) onto 256 CUs one at a time (~2.8 us per
-  // 32-k stage), plus the partial tiles written and read back at ~4 TB/s.  Round 4's estimate (rounds x
-  // the longer split) missed that the second product's units start as soon as the first's free their CU:
-  // round 5 (tools/ab_enc_splits.py) configs[2] (3, 3) 136.9 vs its (2, 1) 141.7 us, configs[1] (8, 7)
-  // 30.0 vs (5, 4) 33.8, configs[3] (4, 1) 101.4 vs (8, 1) 106.2; the headline and configs[4] unchanged.
-  // Memoised per shape (at most kMemo shapes; a full memo starts over).  A pair whose lower bound — its
-  // first product's rounds, or all its work spread evenly over the CUs, plus its traffic — is no better
-  // than the best found is not simulated: the full search is up to 32 x 32 pairs of b t2 heap steps
-  // each (~5e5 at C = 2048), the pruned one a few percent of that.
-  constexpr size_t kMemo = 64;
-  static std::mutex mu;
-  static std::map<std::pair<int64_t, int64_t>, std::pair<int, int>> memo;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = memo.find({E, C});
-    if (it != memo.end()) {
-      pl.s1 = it->second.first;
-      pl.s2 = it->second.second;
-    } else {
-      double best = 1e300;
-      pl.s1 = pl.s2 = 1;
-      std::vector<int64_t> slot(256);
-      for (int a = 1; a <= 32; ++a)
-        for (int b = 1; b <= 32; ++b) {
-          const int64_t p1 = (st1 + a - 1) / a, p2 = (st2 + b - 1) / b;
-          if ((st1 + p1 - 1) / p1 != a || (st2 + p2 - 1) / p2 != b) continue;  // no empty split
-          const int64_t n1 = (int64_t)a * pl.t1, n2 = (int64_t)b * pl.t2;
-          const int64_t q = n1 / 256, r = n1 % 256;
-          const double traffic = ((double)a * C * E + (double)b * C2 * C) * 8.0 / 4.0e6;
-          const int64_t lb = std::max<int64_t>((q + (r ? 1 : 0)) * p1, (n1 * p1 + n2 * p2 + 255) / 256);
-          if ((double)lb * 2.8 + traffic >= best) continue;  // cannot beat the best: skip the simulation
-          for (int i = 0; i < 256; ++i) slot[i] = (q + (i < r ? 1 : 0)) * p1;  // the first product round robin
-          std::make_heap(slot.begin(), slot.end(), std::greater<int64_t>());
-          int64_t span = (q + (r ? 1 : 0)) * p1;
-          for (int64_t i = 0; i < n2; ++i) {  // the second product onto the earliest free CU
-            std::pop_heap(slot.begin(), slot.end(), std::greater<int64_t>());
-            slot.back() += p2;
-            span = slot.back() > span ? slot.back() : span;
-            std::push_heap(slot.begin(), slot.end(), std::greater<int64_t>());
-          }
-          const double cost = (double)span * 2.8 + traffic;
-          if (cost < best) {
-            best = cost;
-            pl.s1 = a;
-            pl.s2 = b;
-          }
-        }
-      if (memo.size() >= kMemo) memo.clear();
-      memo[{E, C}] = {pl.s1, pl.s2};
-    }
-  }
-  // lab knobs enc_s1 / enc_s2 (0: the planner's): force a split count (the chunks cover K, none empty)
-  if (mrp_host::tuning().enc_s1 > 0) pl.s1 = (int)(mrp_host::tuning().enc_s1 < st1 ? mrp_host::tuning().enc_s1 : st1);
-  if (mrp_host::tuning().enc_s2 > 0) pl.s2 = (int)(mrp_host::tuning().enc_s2 < st2 ? mrp_host::tuning().enc_s2 : st2);
-  pl.kc1 = ((st1 + pl.s1 - 1) / pl.s1) * BK;
-  pl.kc2 = ((st2 + pl.s2 - 1) / pl.s2) * BK;
-  pl.s1 = (int)((st1 * BK + pl.kc1 - 1) / pl.kc1);  // the splits the chunks give (no empty one)
-  pl.s2 = (int)((st2 * BK + pl.kc2 - 1) / pl.kc2);
-  auto al = [](int64_t v) { return (v + 63) / 64 * 64; };  // 256-byte segments
-  int64_t o = 0;
-  pl.off_dzT = o;
-  o += al(C2 * E * 3 / 2);  // dz^T in fp32, or its packed split image (6 bytes per element)
-  pl.off_p1 = o;
-  o += al((int64_t)pl.s1 * C * E);
-  pl.off_p2 = o;
-  o += al((int64_t)pl.s2 * C2 * C);
-  pl.off_p2b = o;
-  const int64_t nb2 = (int64_t)pl.s2 > (E + 63) / 64 ? pl.s2 : (E + 63) / 64;  // db2 partials: splits or edge blocks
-  o += al(nb2 * C2);
-  pl.bytes = o * 4;
-  return pl;
-}
-
-// blocks [0, nb1): one hidden unit each -> dW1 / db1; blocks [nb1, ...): 1024
-// outputs of dW2 each (and, in the first 2C / 256 of them, 256 of db2)
-__global__ void __launch_bounds__(256) encoder_bwd_reduce(const float* __restrict__ p1, int s1,
-                                                          const float* __restrict__ hT, const float* __restrict__ pose,
-                                                          int E, int C, float* __restrict__ dw1,
-                                                          float* __restrict__ db1, int nb1,
-                                                          const f4* __restrict__ p2, const float* __restrict__ p2b,
-                                                          int s2, int s2b, f4* __restrict__ dw2, float* __restrict__ db2) {
-  if ((int)blockIdx.x < nb1) {
-    // one workgroup per hidden unit u: wave w's lanes walk edges 64 w + lane + 256 k, summing the dh^T
-    // partials in split order, masking by the ReLU and accumulating d pose^T and d in registers; a
-    // fixed lane butterfly per wave, the four waves' sums added in wave order, and dW1[u] / db1[u]
-    // written directly (no per-edge-block partials, no final launch)
-    __shared__ float wsum[4][kNin + 1];
-    const int u = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t plane = (int64_t)C * E;
-    const float* p1u = p1 + (int64_t)u * E;
-    const float* hTu = hT + (int64_t)u * E;
-    float acc[kNin + 1];
-#pragma unroll
-    for (int i = 0; i <= kNin; ++i) acc[i] = 0.f;
-#pragma unroll 2
-    for (int e = threadIdx.x; e < E; e += 256) {
-      float dh;
-      if (s1 <= 8) {  // every partial's load issued before the sums (clamped index, no branch per load)
-        float pv[8];
-#pragma unroll
-        for (int sp = 0; sp < 8; ++sp) pv[sp] = p1u[(int64_t)(sp < s1 ? sp : s1 - 1) * plane + e];
-        dh = pv[0];
-#pragma unroll
-        for (int sp = 1; sp < 8; ++sp) dh = sp < s1 ? dh + pv[sp] : dh;
-      } else {
-        dh = p1u[e];
-        for (int sp = 1; sp < s1; ++sp) dh += p1u[(int64_t)sp * plane + e];
-      }
-      const float d = hTu[e] > 0.f ? dh : 0.f;
-      const float* pr = pose + (int64_t)e * kNin;
-#pragma unroll
-      for (int i = 0; i < kNin; ++i) acc[i] = fmaf(d, pr[i], acc[i]);
-      acc[kNin] += d;
-    }
-#pragma unroll
-    for (int i = 0; i <= kNin; ++i)
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc[i] += __shfl_xor(acc[i], o, 64);
-    if (lane <= kNin) {
-      float v = acc[0];
-#pragma unroll
-      for (int i = 1; i <= kNin; ++i) v = lane == i ? acc[i] : v;
-      wsum[w][lane] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x <= kNin) {
-      const float v = ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
-      if (threadIdx.x < kNin)
-        dw1[(int64_t)u * kNin + threadIdx.x] = v;
-      else
-        db1[u] = v;
-    }
-    return;
-  }
-  const int b = blockIdx.x - nb1;
-  const int64_t n4 = (int64_t)2 * C * C / 4;
-  const int64_t e4 = (int64_t)b * 256 + threadIdx.x;
-  if (e4 < n4) {
-    f4 v;
-    if (s2 <= 8) {
-      f4 pv[8];
-#pragma unroll
-      for (int sp = 0; sp < 8; ++sp) pv[sp] = p2[(int64_t)(sp < s2 ? sp : s2 - 1) * n4 + e4];
-      v = pv[0];
-#pragma unroll
-      for (int sp = 1; sp < 8; ++sp) v = sp < s2 ? v + pv[sp] : v;
-    } else {
-      v = p2[e4];
-      for (int sp = 1; sp < s2; ++sp) v += p2[(int64_t)sp * n4 + e4];
-    }
-    dw2[e4] = v;
-  }
-  const int64_t m = (int64_t)b * 256 + threadIdx.x;
-  if (m < 2 * C) {
-    float v = p2b[m];
-    for (int sp = 1; sp < s2b; ++sp) v += p2b[(int64_t)sp * 2 * C + m];
-    db2[m] = v;
-  }
-}
-
-}  // namespace mrp_cs
-
-extern "C" int64_t mrp_edge_encoder_bwd_fused_workspace(int32_t num_edges, int32_t C) {
-  if (num_edges <= 0 || C <= 0 || num_edges % BK != 0 || C % 32 != 0) return 0;
-  return mrp_cs::enc_plan(num_edges, C).bytes;
-}
-
-extern "C" int mrp_edge_encoder_bwd_fused(const float* dz, const float* w2T, const void* w2T_packed, const float* hT,
-                                          const float* pose, int32_t num_edges, int32_t C, float* dw1, float* db1,
-                                          float* dw2, float* db2, void* workspace, int64_t workspace_bytes,
-                                          void* stream) {
-  using namespace mrp_cs;
-  if (num_edges < 0 || C < 0) return hipErrorInvalidValue;
-  if (C == 0) return hipSuccess;
-  if (!dw1 || !db1 || !dw2 || !db2) return hipErrorInvalidValue;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t E = num_edges, C2 = 2 * (int64_t)C;
-  if (E == 0) {  // empty sums
-    if (hipMemsetAsync(dw1, 0, (size_t)C * kNin * 4, st) != hipSuccess ||
-        hipMemsetAsync(db1, 0, (size_t)C * 4, st) != hipSuccess ||
-        hipMemsetAsync(dw2, 0, (size_t)C2 * C * 4, st) != hipSuccess || hipMemsetAsync(db2, 0, (size_t)C2 * 4, st) != hipSuccess)
-      return hipErrorUnknown;
-    return hipSuccess;
-  }
-  if (E % BK != 0 || C % 32 != 0) return hipErrorNotSupported;
-  if (!dz || !w2T || !hT || !pose || !aligned16(dz) || !aligned16(w2T) || !aligned16(hT) || !aligned16(dw2))
-    return hipErrorInvalidValue;
-  const EncPlan pl = enc_plan(E, C);
-  if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < pl.bytes) return hipErrorInvalidValue;
-  float* ws = static_cast<float*>(workspace);
-  float* dzT = ws + pl.off_dzT;
-  // W2^T's packed image (mrp_compress_split_pack(w2, C, 1, C, 2C)): the dh^T product reads its A by
-  // LDS-DMA instead of splitting W2^T in every workgroup; and (enc_bwd_psa 2, the default) dz^T is
-  // written as a packed image too (dzT_pack, with db2's partials), so the dW2 product reads both its
-  // operands' A side pre-split.  enc_bwd_psa 0: both split in the kernel, 1: only W2^T pre-split.
-  const int mode = mrp_host::tuning().enc_bwd_psa;
-  const bool psa1 = w2T_packed != nullptr && aligned16(w2T_packed) && mode >= 1 && (int64_t)C * C2 * 6 < kOffMax;
-  const bool psa2 = psa1 && mode >= 2 && C2 * E * 6 < kOffMax;
-  hipError_t e;
-  if (psa2) {
-    hipLaunchKernelGGL(dzT_pack, dim3((unsigned)((C2 + 63) / 64), (unsigned)((E + 63) / 64)), dim3(256), 0, st, dz,
-                       num_edges, (int)C2, reinterpret_cast<u4*>(dzT), ws + pl.off_p2b);
-    e = hipGetLastError();
-  } else {
-    e = (hipError_t)mrp_edge_encoder_bwd_prep(dz, num_edges, C, dzT, E, stream);
-  }
-  if (e != hipSuccess) return e;
-  NTArgs a1 = {};  // dh^T (C x E) = W2^T (C x 2C) . dz^T: rows u, k = j
-  a1.g = w2T;
-  a1.gs = C * C2;
-  a1.s0 = dz;
-  a1.s0s = E * C2;
-  a1.s1 = dz;
-  a1.s1s = E * C2;
-  a1.n0 = (int32_t)E;
-  a1.P = (int32_t)C2;
-  a1.out = ws + pl.off_p1;
-  a1.outb = nullptr;
-  a1.ktot = C2;
-  a1.kchunk = pl.kc1;
-  a1.M = C;
-  a1.N = (int32_t)E;
-  a1.mtiles = (int32_t)((C + NTGeo<4>::TM - 1) / NTGeo<4>::TM);
-  a1.ntiles = (int32_t)((E + TN - 1) / TN);
-  a1.ap = psa1 ? static_cast<const u4*>(w2T_packed) : nullptr;
-  NTArgs a2 = {};  // dW2 (2C x C) = dz^T (2C x E) . h: rows j, k = e; row sums = db2
-  a2.g = dzT;
-  a2.gs = C2 * E;
-  a2.s0 = hT;
-  a2.s0s = (int64_t)C * E;
-  a2.s1 = hT;
-  a2.s1s = (int64_t)C * E;
-  a2.n0 = C;
-  a2.P = (int32_t)E;
-  a2.out = ws + pl.off_p2;
-  a2.outb = psa2 ? nullptr : ws + pl.off_p2b;  // psa2: db2's partials came from dzT_pack
-  a2.ap = psa2 ? reinterpret_cast<const u4*>(dzT) : nullptr;
-  a2.ktot = E;
-  a2.kchunk = pl.kc2;
-  a2.M = (int32_t)C2;
-  a2.N = C;
-  a2.mtiles = (int32_t)((C2 + NTGeo<4>::TM - 1) / NTGeo<4>::TM);
-  a2.ntiles = (int32_t)((C + TN - 1) / TN);
-  const int grid1 = pl.t1 * pl.s1, grid2 = pl.t2 * pl.s2;
-  using GN = NTGeo<4>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_dual_mf16),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, GN::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
-  static const hipError_t attr_p = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_dual_psa1),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, GN::LDS_BYTES);
-  if (attr_p != hipSuccess) return attr_p;
-  static const hipError_t attr_p2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_dual_psa2),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, GN::LDS_BYTES);
-  if (attr_p2 != hipSuccess) return attr_p2;
-  a1.group = a2.group = mrp_host::tuning().nt_group;
-  if (psa2)
-    hipLaunchKernelGGL(gemm_nt_dual_psa2, dim3((unsigned)(grid1 + grid2)), dim3(GN::THREADS), GN::LDS_BYTES, st, a1,
-                       a2, grid1);
-  else if (psa1)
-    hipLaunchKernelGGL(gemm_nt_dual_psa1, dim3((unsigned)(grid1 + grid2)), dim3(GN::THREADS), GN::LDS_BYTES, st, a1,
-                       a2, grid1);
-  else
-    hipLaunchKernelGGL(gemm_nt_dual_mf16, dim3((unsigned)(grid1 + grid2)), dim3(GN::THREADS), GN::LDS_BYTES, st, a1,
-                       a2, grid1);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  const int nb1 = C;
-  const int64_t nb2 = (C2 * C / 4 + 255) / 256;  // >= 2C / 256 blocks: db2 rides along
-  hipLaunchKernelGGL(encoder_bwd_reduce, dim3((unsigned)(nb1 + nb2)), dim3(256), 0, st, ws + pl.off_p1, pl.s1, hT, pose,
-                     num_edges, C, dw1, db1, nb1, reinterpret_cast<const f4*>(ws + pl.off_p2), ws + pl.off_p2b,
-                     pl.s2, psa2 ? (int)((E + 63) / 64) : pl.s2, reinterpret_cast<f4*>(dw2), db2);
-  return hipGetLastError();
 }

@@ -488,17 +488,6 @@ bool operand_ok(const void* p, int64_t ns, int64_t ps, int32_t C, int32_t P) {
   return p != nullptr && aligned16(p) && (ns & 3) == 0 && (ps & 3) == 0 && ps >= C && ns >= (int64_t)P * ps;
 }
 
-// one instantiation per kernel, so each kernel's LDS attribute is set (once) for that kernel
-template <int NP>
-hipError_t launch_np(const Args& a, int64_t grid, hipStream_t st) {
-  using G = ClGeo<NP>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_cl_split<NP>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_cl_split<NP>, dim3((unsigned)grid), dim3(THREADS), G::LDS_BYTES, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch(Args a, int parts, hipStream_t st) {
   // 32-bit offsets: the packed image (LDS-DMA) and the pixel-row index
   if ((int64_t)a.M * a.K * 6 >= kOffMax || a.nrows >= kOffMax) return hipErrorNotSupported;
@@ -506,17 +495,10 @@ hipError_t launch(Args a, int parts, hipStream_t st) {
   const int64_t grid = (int64_t)a.mtiles * ((a.nrows + TN - 1) / TN);
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   a.group = mrp_host::tuning().gemm_group;
-  return parts == 3 ? launch_np<3>(a, grid, st) : parts == 2 ? launch_np<2>(a, grid, st) : launch_np<1>(a, grid, st);
-}
-
-template <int NP>
-hipError_t launch_wg_np(const WArgs& a, int64_t grid, hipStream_t st) {
-  using G = WgGeo<NP>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wg_cl_split<NP>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(gemm_wg_cl_split<NP>, dim3((unsigned)grid), dim3(THREADS), G::LDS_BYTES, st, a);
-  return hipGetLastError();
+  return dispatch_parts(parts, [&](auto np) {
+    constexpr int NP = decltype(np)::value;
+    return launch_lds<gemm_cl_split<NP>>(ClGeo<NP>::LDS_BYTES, dim3((unsigned)grid), dim3(THREADS), st, a);
+  });
 }
 
 }  // namespace mrp_cscl
@@ -644,9 +626,10 @@ extern "C" int mrp_compress_bwd_weight_split_cl(const float* gy, int64_t gy_node
   const int64_t grid = (int64_t)a.mtiles * a.ntiles * ns + a.ndb;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   a.group = mrp_host::tuning().nt_group;
-  const hipError_t e = parts == 3  ? launch_wg_np<3>(a, grid, st)
-                       : parts == 2 ? launch_wg_np<2>(a, grid, st)
-                                    : launch_wg_np<1>(a, grid, st);
+  const hipError_t e = dispatch_parts(parts, [&](auto np) {
+    constexpr int NP = decltype(np)::value;
+    return launch_lds<gemm_wg_cl_split<NP>>(WgGeo<NP>::LDS_BYTES, dim3((unsigned)grid), dim3(THREADS), st, a);
+  });
   if (e != hipSuccess || ns <= 1) return e;
   return split_sum(pl.out, ns, M, N, gw, pl.outb, ns, gbias, st);
 }

@@ -198,7 +198,7 @@ extern "C" int mrp_edge_encoder_bwd(const float* dz, const float* dh, const floa
 // ------------------------------------------------------------------------------------------------
 // Backward in the transposed layout of the split-bf16 training path (encoder.py, EdgeEncoderSplitFunction):
 // the forward wrote h^T (C, E); the two GEMMs dh^T = W2^T dz^T and dW2 = dz^T h run on the split-bf16
-// weight-gradient kernel (compress_split.hip, mrp_edge_encoder_bwd_split, which also takes db2 as the
+// weight-gradient kernel (encoder_bwd_split.hip, mrp_edge_encoder_bwd_split, which also takes db2 as the
 // row sums of dz^T), whose operands are rows with k contiguous — so dz is first transposed:
 //   mrp_edge_encoder_bwd_prep:  dzT[j][e] = dz[e][j]
 //   mrp_edge_encoder_bwd_t:     dpre = dh^T (.) [h^T > 0];  dw1[k][i] = sum_e dpre[k][e] pose[e][i],

@@ -1,12 +1,14 @@
 // gemm_common.hpp — what more than one of the GEMM translation units (compress_gemm.hip,
-// compress_split.hip, compress_split_cl.hip, compress_half.hip, compress_half_cl.hip, encoder_split.hip)
-// uses: vector types,
-// the buffer resource, the workgroup -> tile order, the 16-bit LDS image layouts, and the host side of
-// the split-K weight gradients (planner, workspace placement, the sum of the partial tiles).
+// compress_split.hip, encoder_bwd_split.hip, compress_split_cl.hip, compress_half.hip, compress_half_cl.hip,
+// encoder_split.hip) uses: vector types, the buffer resource, the workgroup -> tile order, the 16-bit LDS
+// image layouts, the launch of a kernel with dynamic LDS, the part-count dispatch, and the host side of the
+// split-K weight gradients (planner, workspace placement, the sum of the partial tiles).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace mrp_gemm {
 
@@ -60,6 +62,27 @@ __device__ __forceinline__ uint32_t rowoff(int row, int chunk) {
 constexpr int64_t kOffMax = (int64_t)1 << 31;  // buffer offsets are 32-bit; keep every one below 2^31
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Launch kernel K with lds_bytes of dynamic LDS.  K is a template argument, so each kernel has its own
+// instantiation and its dynamic-LDS attribute is set once per process, before its first launch.  Returns
+// that call's error, else the launch's.
+template <auto K, typename... A>
+hipError_t launch_lds(int lds_bytes, dim3 grid, dim3 block, hipStream_t st, A... a) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(K, grid, block, lds_bytes, st, a...);
+  return hipGetLastError();
+}
+
+// f(std::integral_constant<int, parts>) for a part count the caller has validated (1..3): the run-time
+// count of bf16 parts -> the compile-time NP of a kernel or launcher
+template <class F>
+auto dispatch_parts(int parts, F f) {
+  if (parts == 3) return f(std::integral_constant<int, 3>{});
+  if (parts == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 1>{});
+}
 
 // compress_split.hip: the split-K planner of the 256 x 128-tile, 32-k-stage weight-gradient kernels
 int nt_splits(int64_t tiles, int64_t ktot, int64_t M, int64_t N, int64_t* kchunk);

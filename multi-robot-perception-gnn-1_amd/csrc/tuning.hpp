@@ -42,7 +42,7 @@ struct Tuning {
   // mrp_edge_encoder_fwd_split (encoder_split.hip): -1 per shape, 1 = 4 waves, 3 = 8 waves per workgroup
   int edge_split_v = -1;
   int edge_allx = 1;  // mrp_edge_encoder_fwd_split: all hidden blocks before z where they fit LDS (0 off)
-  // split-bf16 weight-gradient (NT) kernel: 4 (the default where C >= 1024) the compress weight gradient
+  // split-bf16 weight-gradient (NT) kernel (split_nt.hpp's bodies; compress_split.hip): 4 (the default where C >= 1024) the compress weight gradient
   // with dy split once into a packed image (split_rows + gemm_nt_psa) where the image fits 32-bit
   // offsets, else (and for the encoder's products) 3 (the default below C = 1024): the 32-k-stage form
   // on 16x16x32 MFMAs splitting both operands
@@ -53,7 +53,7 @@ struct Tuning {
   // at configs[2] and [3])
   int gemm_group = 4;
   int nt_group = 0;
-  // mrp_edge_encoder_bwd_fused, given W2^T's packed image: 2 = both products read their A operand
+  // mrp_edge_encoder_bwd_fused (encoder_bwd_split.hip), given W2^T's packed image: 2 = both products read their A operand
   // pre-split (W2^T's image; dz^T written as an image by dzT_pack), 1 = only W2^T's, 0 = neither
   int enc_bwd_psa = 2;
   int enc_s1 = 0, enc_s2 = 0;  // mrp_edge_encoder_bwd_fused: split counts of its two products (0: planner)

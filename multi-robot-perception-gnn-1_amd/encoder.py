@@ -10,8 +10,8 @@ once per weight version (:func:`packed_weights`):
 * inference (no gradient wanted): ONE kernel, ``mrp_edge_encoder_fwd_split`` — h never written;
 * training (:class:`EdgeEncoderSplitFunction`, E % 32 == 0 and C % 32 == 0 — every reference
   configuration): the same kernel also writes h^T for the backward; the backward's two GEMMs
-  (``dh^T = W2^T dz^T``, ``dW2 = dz^T h`` with db2) run on the split-bf16 weight-gradient kernel of
-  ``compress_split.hip`` (one launch of both, or two streams), the ReLU mask, dW1 and db1 in one HIP
+  (``dh^T = W2^T dz^T``, ``dW2 = dz^T h`` with db2) run on the split-bf16 NT product of
+  ``encoder_bwd_split.hip`` (one launch of both, or two streams), the ReLU mask, dW1 and db1 in one HIP
   pass, the pose gradient (when poses require grad) on ``mrp_edge_encoder_bwd_pose``;
 * any other E or C (:class:`EdgeEncoderPaddedFunction`, and inference with C % 32 != 0): the same
   kernels on operands zero-padded to multiples of 32 (:func:`padded_weights`) — every padded term a

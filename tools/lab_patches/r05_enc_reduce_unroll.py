@@ -3,6 +3,6 @@
 import os
 
 U = int(os.environ.get("ENC_UNROLL", "8"))
-PATCH = [("compress_split.hip", """#pragma unroll 2
+PATCH = [("encoder_bwd_split.hip", """#pragma unroll 2
     for (int e = threadIdx.x; e < E; e += 256) {""", """#pragma unroll %d
     for (int e = threadIdx.x; e < E; e += 256) {""" % U)]

@@ -80,10 +80,24 @@ extern "C" {
  *   - every edge's source lies in its destination's graph;
  *   - MRP_GRAPH_REGULAR(k): every node has exactly k in-edges, so node v's CSR row is
  *     [k*v, k*(v+1)) (indptr is then not read by the forward);
- *   - MRP_GRAPH_COMPLETE: the edge numbering below. */
+ *   - MRP_GRAPH_COMPLETE: the edge numbering below;
+ *   - MRP_GRAPH_SIMPLE: no two CSR entries share a (source, destination) pair.
+ *
+ * MRP_GRAPH_SIMPLE is a batch described by the CSR arrays exactly as MRP_GRAPH_CSR, with that one
+ * additional promise (a range-limited or drop-out frame has it by construction;
+ * mrp_frame_graph_build_range builds such graphs).  Self-loops, graphs of fewer than max_nodes nodes
+ * and nodes of in-degree 0 are allowed.  num_edges is the number of rows of gb / grad_gb and may
+ * exceed indptr[num_nodes]: edge ids need not cover every row (src and eid hold at least
+ * indptr[num_nodes] entries and must be non-NULL when num_edges > 0).  The backward writes every
+ * grad_gb row that no CSR entry names as zeros.  Every entry point handles the kind as it handles
+ * MRP_GRAPH_CSR (same kernels, same bits) except the NCHW backward of graphs with max_nodes 9..16,
+ * which runs film_bwd_mfma in its CSR-row form where that kernel's conditions hold (P % 64 == 0,
+ * aligned 4-element slices, 32-bit row offsets; knobs "bwd_regular_mfma", "bwd_half_mfma"): the weight
+ * tile of a destination is then a plain scatter of its row, which is what the promise is for. */
 enum mrp_graph_kind {
     MRP_GRAPH_CSR = 0,
-    MRP_GRAPH_COMPLETE = 1
+    MRP_GRAPH_COMPLETE = 1,
+    MRP_GRAPH_SIMPLE = 3 /* 2 is the low byte of MRP_GRAPH_REGULAR(k) */
 };
 /* MRP_GRAPH_REGULAR(k): a CSR graph in which every node has exactly k in-edges (k-NN graphs).  The
  * CSR arrays are read as for MRP_GRAPH_CSR; the backward for graphs of more than 8 nodes then keeps
@@ -119,7 +133,8 @@ enum mrp_agg_mode {
  *   src, eid   (num_edges) int32
  *   graph_off  (num_graphs + 1) int32 node offsets of the batched graphs
  *   max_nodes  max_b (graph_off[b+1] - graph_off[b]), 0..MRP_MAX_NODES (host-known)
- *   graph_kind MRP_GRAPH_CSR, MRP_GRAPH_COMPLETE or MRP_GRAPH_REGULAR(k) (see enum mrp_graph_kind)
+ *   graph_kind MRP_GRAPH_CSR, MRP_GRAPH_COMPLETE, MRP_GRAPH_SIMPLE or MRP_GRAPH_REGULAR(k) (see enum
+ *              mrp_graph_kind)
  *   out        (num_nodes, C, P) fp32, node stride out_node_stride (elements)
  */
 int mrp_film_mean_fwd(const float* x, int64_t x_node_stride,
@@ -772,6 +787,37 @@ int mrp_edge_encoder_bwd(const float* dz, const float* dh, const float* h, const
 int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int32_t knn_k,
                           float* edge_pose, int32_t* indptr, int32_t* src, int32_t* eid,
                           int32_t* graph_off, void* stream);
+
+/*
+ * Range-limited / drop-out frames built on the device: graphs of kind MRP_GRAPH_SIMPLE.
+ *
+ *   poses      as above
+ *   active     (num_graphs * n) bytes, nonzero = the robot takes part; NULL = all do
+ *   knn_k      0: every robot in range; k (1 <= k < n): each destination keeps at most the k nearest
+ *              of those (ties to the lower index)
+ *   max_range  edge u->v exists iff u != v, both robots are active and d(u, v) <= max_range, with d the
+ *              float64 distance of the translations, sqrt((dx^2 + dy^2) + dz^2) as in the k-NN rule;
+ *              the comparison is inclusive, a NaN distance gives no edge, +inf means unlimited
+ *   edge_pose  (num_graphs*n*(n-1), 9): every ordered pair's relative pose, present or not — the
+ *              rows, numbering and bits of mrp_frame_graph_build(knn_k = 0)
+ *   indptr     (num_graphs*n + 1); src, eid (capacity num_graphs*n*(n-1), indptr[num_graphs*n] used):
+ *              the existing edges only, destination-major with sources ascending, eid = the complete
+ *              graph's id b*n*(n-1) + u*(n-1) + (v < u ? v : v-1)
+ *   graph_off  (num_graphs + 1): graph_off[b] = b*n — every robot stays a node; an inactive one has
+ *              no edge in or out
+ *   workspace  mrp_frame_graph_build_range_workspace(num_graphs, n) bytes of device memory, 4-byte
+ *              aligned (the in-degrees' block totals of the prefix sum)
+ * The aggregation calls then take num_edges = num_graphs*n*(n-1) (the rows of gb) and kind
+ * MRP_GRAPH_SIMPLE.  Three launches on `stream`, no host read-back and no allocation: capturable, and
+ * deterministic (the prefix sum is a fixed tree, no atomics).  Any output pointer may be NULL to skip it.
+ * Returns hipErrorInvalidValue before any launch for n > MRP_MAX_NODES, knn_k < 0 or knn_k >= n (n > 0), a
+ * NaN or negative max_range, a workspace that is NULL or too small, or sizes beyond int32.
+ */
+int mrp_frame_graph_build_range(const float* poses, const uint8_t* active, int32_t num_graphs, int32_t n,
+                                int32_t knn_k, double max_range, float* edge_pose, int32_t* indptr,
+                                int32_t* src, int32_t* eid, int32_t* graph_off, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+int64_t mrp_frame_graph_build_range_workspace(int32_t num_graphs, int32_t n);
 
 /* Experiment knobs of the launchers (kernel-lab sweeps; not needed for normal use; process-wide,
  * not thread-safe).  Returns hipErrorInvalidValue for an unknown name or a value out of range;

@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "mrp_edge_encoder_bwd_pose_workspace",
     "mrp_edge_encoder_bwd_pose",
     "mrp_frame_graph_build",
+    "mrp_frame_graph_build_range",
+    "mrp_frame_graph_build_range_workspace",
     "mrp_stream_copy",
     "mrp_stream_join",
     "mrp_tuning_set",
@@ -98,6 +100,7 @@ DTYPE_BF16 = 1
 DTYPE_F16 = 2
 GRAPH_CSR = 0
 GRAPH_COMPLETE = 1
+GRAPH_SIMPLE = 3  # CSR arrays in which no two entries share a (source, destination) pair
 
 
 MAX_REGULAR_K = 8  # largest in-degree the per-edge-slot backward handles
@@ -278,6 +281,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_edge_encoder_bwd.restype = ctypes.c_int
     lib.mrp_frame_graph_build.argtypes = [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]
     lib.mrp_frame_graph_build.restype = ctypes.c_int
+    lib.mrp_frame_graph_build_range.argtypes = [_P, _P, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P, _P, _P, _P,
+                                                _I64, _P]
+    lib.mrp_frame_graph_build_range.restype = ctypes.c_int
+    lib.mrp_frame_graph_build_range_workspace.argtypes = [_I32, _I32]
+    lib.mrp_frame_graph_build_range_workspace.restype = ctypes.c_int64
     lib.mrp_stream_copy.argtypes = [_P, _P, _I64, _P]
     lib.mrp_stream_copy.restype = ctypes.c_int
     lib.mrp_stream_join.argtypes = [_P, _P]

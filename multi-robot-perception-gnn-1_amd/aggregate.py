@@ -290,6 +290,13 @@ def _forward(x, gb, csr, mode, out, epilogue=None):
     return out
 
 
+def _alloc_grad_gb(csr: GraphCSR, C: int, device) -> torch.Tensor:
+    """grad_gb (E, C, 2).  The kernels write every row an edge id names; a masked graph's arrays leave rows
+    unnamed, which kind GRAPH_SIMPLE has the library clear and the GRAPH_CSR route has cleared here."""
+    sparse = getattr(csr, "sparse_eid", False) and csr.graph_kind != _lib.GRAPH_SIMPLE
+    return (torch.zeros if sparse else torch.empty)((csr.num_edges, C, 2), device=device, dtype=torch.float32)
+
+
 def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR,
                        mode: int, need_dx: bool, need_dgb: bool, grad_x_base: Optional[torch.Tensor] = None,
                        epilogue: Optional[EpilogueSpec] = None, pixel_major: bool = True):
@@ -312,7 +319,7 @@ def film_mean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: Optional[tor
             grad_x_base = grad_x_base.to(dtype)
         grad_x_base, bs = _as_node_major(grad_x_base)
     dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
-    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    dgb = _alloc_grad_gb(csr, C, x.device) if need_dgb else None
     xs = 0
     if need_dgb and (mode & ~_lib.GB_LOGITS) != _lib.MODE_COPY_MEAN:
         x, xs = _as_node_major(x)
@@ -363,7 +370,7 @@ def _backward_cl(grad_out, x, gb, csr, mode, need_dx, need_dgb, grad_x_base, epi
             grad_x_base = grad_x_base.to(dtype)
         base, bs, bp = _as_pixel_major(grad_x_base)
     dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype, memory_format=torch.channels_last) if need_dx else None
-    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    dgb = _alloc_grad_gb(csr, C, x.device) if need_dgb else None
     xs, xp = pixel_strides(x)
     dxs, dxp = pixel_strides(dx) if dx is not None else (0, 0)
     if gb is not None:

@@ -15,6 +15,7 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "film_mean_cl_fwd.hip", "film_mean_cl_bwd.hip",
                                                     "film_mean_bwd_half_1_8.hip", "film_mean_bwd_half_9_12.hip",
                                                     "film_mean_bwd_half_13_16.hip", "film_mean_bwd_half_mfma.hip",
+                                                    "film_mean_bwd_rows_mfma.hip",
                                                     "film_mean_fwd_bf16.hip",
                                                     "film_mean_fwd_f16.hip", "film_mean_bwd.hip",
                                                     "edge_encoder.hip", "frame_graph.hip",

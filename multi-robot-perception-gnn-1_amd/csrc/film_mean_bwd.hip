@@ -1,6 +1,6 @@
 // film_mean_bwd.hip — backward C ABI (mrp_film_mean_bwd).  The kernel launches are instantiated
-// in film_mean_bwd_{1_8,9_12,13_16}.hip (split by graph size so they compile in parallel) and, for 16-bit
-// features, film_mean_bwd_half_{1_8,9_12,13_16,mfma}.hip;
+// in film_mean_bwd_{1_8,9_12,13_16}.hip (split by graph size so they compile in parallel), for 16-bit
+// features film_mean_bwd_half_{1_8,9_12,13_16,mfma}.hip, and film_mean_bwd_rows_mfma.hip (MRP_GRAPH_SIMPLE);
 // kernels and design notes: film_mean_kernels.hpp.
 #include "film_mean_kernels.hpp"
 
@@ -18,6 +18,8 @@ Geometry regular_geometry(int C, int P, int vec) {
 }
 
 hipError_t dispatch_bwd(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st) {
+  // the CSR-row form of film_bwd_mfma (MRP_GRAPH_SIMPLE): film_mean_bwd_rows_mfma.hip, every dtype
+  if (g.kernel == MRP_AGG_KERNEL_FILM_BWD_MFMA && g.kmax == 16) return dispatch_bwd_rows_mfma(dtype, a, g, st);
   if (dtype != MRP_DTYPE_F32) {  // 16-bit features: film_mean_bwd_half_*.hip
     if (nt >= 1 && nt <= 8) return dispatch_bwd_half_1_8(dtype, nt, complete, a, g, st);
     if (nt >= 9 && nt <= 12) return dispatch_bwd_half_9_12(dtype, nt, complete, a, g, st);
@@ -159,7 +161,10 @@ int film_bwd_plan(int32_t dtype, const void* grad_out, int64_t g_node_stride, co
                       mode))
     return hipErrorInvalidValue;
   const bool copy = mode == MRP_AGG_COPY_MEAN;
-  zero_dgb = grad_gb != nullptr && num_edges > 0 && C > 0 && (copy || num_nodes == 0 || P == 0 || agg_scale == 0.f);
+  // MRP_GRAPH_SIMPLE: edge ids need not cover grad_gb's rows, and the rows no CSR entry names are zero
+  const bool simple = graph_kind == MRP_GRAPH_SIMPLE;
+  zero_dgb = grad_gb != nullptr && num_edges > 0 && C > 0 &&
+             (copy || num_nodes == 0 || P == 0 || agg_scale == 0.f || simple);
   const bool want_dgb = grad_gb != nullptr && !copy && num_edges > 0 && agg_scale != 0.f;
   const bool want_dx = grad_x != nullptr;
   if (!want_dgb && !want_dx) return hipSuccess;
@@ -216,10 +221,11 @@ int film_bwd_plan(int32_t dtype, const void* grad_out, int64_t g_node_stride, co
     g.lds = lds_bwd(max_nodes, g.cpb, sig_lds);
     g.lds_dx = lds_dx(max_nodes, g.cpb);
   }
-  // film_bwd_mfma: regular graphs of 9..16 nodes and complete graphs, whole pixel groups of 64, 4-element
+  // film_bwd_mfma: regular and simple graphs of 9..16 nodes and complete graphs, whole pixel groups of 64, 4-element
   // slices (vec4: 16-byte aligned fp32, 8-byte aligned 16-bit features; bwd_half_mfma = 0 keeps 16-bit
   // features on film_bwd_dx + the Gram pass)
   const bool mfma_kind = ((max_nodes > 8 && kdeg >= 1 && kdeg <= 8 && tuning().bwd_regular_mfma) ||
+                          (simple && max_nodes > 8 && tuning().bwd_regular_mfma) ||  // the CSR-row form
                           (complete && max_nodes > 8 && tuning().bwd_complete_mfma)) &&
                          (!half || tuning().bwd_half_mfma);
   if (mfma_kind && vec4 && P % 64 == 0) {
@@ -240,7 +246,7 @@ int film_bwd_plan(int32_t dtype, const void* grad_out, int64_t g_node_stride, co
       g.threads = 256;
       g.ncb = (C + g.cpb - 1) / g.cpb;
       kernel = MRP_AGG_KERNEL_FILM_BWD_MFMA;
-      g.kmax = complete ? 1 : (kdeg <= 4 ? 4 : 8);  // film_bwd_mfma's KMAX
+      g.kmax = complete ? 1 : simple ? 16 : (kdeg <= 4 ? 4 : 8);  // film_bwd_mfma's KMAX (16: the CSR-row form)
       g.lds = lds_mfma(g.cpb, g.mfma_npb, g.kmax);
       g.lds_dx = 0;
       g.pre2 = 0;

@@ -81,7 +81,8 @@ int mrp_film_mean_bwd_cl(int32_t dtype, const void* grad_out, int64_t g_node_str
   const bool sized = !(num_graphs == 0 || num_nodes == 0 || max_nodes == 0 || C == 0 || P == 0);
   const bool want_dgb = grad_gb != nullptr && gram_wanted(mode, num_edges) && agg_scale != 0.f && sized;
   const bool want_dx = grad_x != nullptr && sized;
-  const bool zero_dgb = grad_gb != nullptr && num_edges > 0 && C > 0 && !want_dgb;
+  // MRP_GRAPH_SIMPLE: the rows of grad_gb that no CSR entry names are zero (cleared before the Gram pass)
+  const bool zero_dgb = grad_gb != nullptr && num_edges > 0 && C > 0 && (!want_dgb || graph_kind == MRP_GRAPH_SIMPLE);
   hipStream_t st = static_cast<hipStream_t>(stream);
 
   // every check before the first enqueue

@@ -1690,7 +1690,11 @@ __device__ __forceinline__ void store_mf4(T* p, mf4 o) {
 
 // Template parameters:
 //   COMPLETE: complete graphs of exactly n = max_nodes nodes with arithmetic edge ids (the reference
-//             topology), else REGULAR(k) graphs (slot (v, j) = CSR position K v + j).
+//             topology), else REGULAR(k) graphs (slot (v, j) = CSR position K v + j) or, KMAX == 16, the
+//             CSR-row form for MRP_GRAPH_SIMPLE graphs (ROWS below): slot (v, j) = CSR position
+//             indptr[v] + j, j < in-degree(v) <= 16.  No two entries share (source, destination), so
+//             column v of Wt is a plain scatter of s_v * gamma_e; the scale s_v = 1 / in-degree(v) (1 for
+//             FILM_SUM and for in-degree 0) is per destination and kept in LDS for the epilogue.
 //   NPB:      nodes per 16-row block: 16 (graphs of 9..16 nodes, one channel per block) or 8 (graphs
 //             of <= 8 nodes: two channels share a block as a block-diagonal system; row/column
 //             16-index vn = 8 h + node, h = channel of the pair).
@@ -1705,7 +1709,9 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   static_assert(NPB == 16 || NPB == 8, "16-row blocks of one or two channels");
   constexpr int CB = 16 / NPB;             // channels per block
   constexpr int CPB = 4 * CPW * CB;        // channels per workgroup
-  constexpr int NS = NPB * KMAX;           // REGULAR edge slots
+  constexpr int NS = NPB * KMAX;           // REGULAR / ROWS edge slots
+  constexpr bool ROWS = !COMPLETE && KMAX == 16;  // CSR rows of a simple graph (MRP_GRAPH_SIMPLE)
+  static_assert(!ROWS || NPB == 16, "the CSR-row form is for graphs of 9..16 nodes");
   constexpr int WR = NPB + 1;              // per-channel Wt / D row stride (floats)
   // per-channel Wt / D stride: the prologue's 32-lane stores (CPB channels x 32 / CPB destinations)
   // land on 32 different banks (NPB = 16: 8 channels 20 banks apart mod 32; unpadded, 272 = 16 mod 32
@@ -1723,6 +1729,7 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   float* Sl = Tt + 4 * 16 * TR;       // [CPB][SS]
   int* slot_u = reinterpret_cast<int*>(Sl + CPB * SS);  // [NS] (REGULAR)
   int* slot_e = slot_u + NS;                              // [NS]
+  float* sv = reinterpret_cast<float*>(slot_e + NS);      // [NPB] (ROWS): the destinations' scales s_v
 
   const int b = blockIdx.x / a.ncb;
   const int cb = blockIdx.x - b * a.ncb;
@@ -1747,13 +1754,29 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
   const int pt = threadIdx.x;
   const bool pitem = pt < CPB * NPB;
   const int pcl = pt % CPB, pv = pt / CPB;
+  using eid_t = typename std::conditional<ROWS, int, int64_t>::type;  // ROWS: 16 slots of 32-bit ids
   int us[NE];
-  int64_t es[NE];
+  eid_t es[NE];
+  int deg = 0;  // ROWS: in-degree of pv (its CSR row length, at most NE slots walked)
   {
     const bool ok = pitem && pv < n && c0 + pcl < a.C;
+    int r0 = 0;
+    if constexpr (ROWS) {
+      const int nd = node0 + (ok ? pv : 0);
+      r0 = a.indptr[nd];
+      deg = ok ? min(max(a.indptr[nd + 1] - r0, 0), NE) : 0;
+    }
 #pragma unroll
     for (int jj = 0; jj < NE; ++jj) {
-      if (COMPLETE) {
+      if constexpr (ROWS) {
+        // an absent slot reads indptr's first word instead (a valid address whatever the row holds; src
+        // and eid may be shorter than num_edges): selected addresses, unconditional loads, as below
+        const bool on = jj < deg;
+        const int sv_ = *(on ? a.src + (r0 + jj) : a.indptr);
+        const int ev = *(on ? a.eid + (r0 + jj) : a.indptr);
+        us[jj] = on ? sv_ - node0 : -1;
+        es[jj] = on ? ev : -1;
+      } else if (COMPLETE) {
         const bool on = ok && jj < n && jj != pv;
         us[jj] = on ? jj : -1;
         es[jj] = on ? complete_eid(ebase, n, jj, pv) : -1;
@@ -1840,24 +1863,36 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
     const float* gsrc = copy ? static_cast<const float*>(a.g) : a.gb;
 #pragma unroll
     for (int jj = 0; jj < NE; ++jj)
-      graw[jj] = gsrc[copy ? 0 : ((es[jj] >= 0 ? es[jj] : 0) * a.C + c0 + pcl) * 2];
+      graw[jj] = gsrc[copy ? 0 : ((int64_t)(es[jj] >= 0 ? es[jj] : 0) * a.C + c0 + pcl) * 2];
 #pragma unroll
     for (int jj = 0; jj < NE; ++jj) {
       float gv = copy ? 1.f : graw[jj];
       if (!copy && a.logits) gv = sigmoidf(gv);
       gm[jj] = __int_as_float(__float_as_int(gv) & -(int)(es[jj] >= 0));  // es < 0 ? +0 : gv, by mask
     }
+    if constexpr (ROWS) {
+      // column pv of Wt: zeros, then one store per row entry (no two share a source).  Both by this
+      // thread, and LDS keeps a wave's accesses in order.
+      const float sp = (a.mode != MRP_AGG_FILM_SUM && deg > 0 ? 1.f / (float)deg : 1.f) * a.agg_scale;
 #pragma unroll
-    for (int u = 0; u < NPB; ++u) {
-      float wv = 0.f;
-      if (COMPLETE) {
-        wv = s * gm[u];
-      } else {
+      for (int u = 0; u < NPB; ++u) Wt[pcl * CS + u * WR + pv] = 0.f;
 #pragma unroll
-        for (int jj = 0; jj < NE; ++jj)  // += in slot order: multi-edges sum like the CSR tile build
-          if (us[jj] == u) wv += s * gm[jj];
+      for (int jj = 0; jj < NE; ++jj)
+        if ((unsigned)us[jj] < (unsigned)n) Wt[pcl * CS + us[jj] * WR + pv] = sp * gm[jj];
+      if (pcl == 0) sv[pv] = sp;
+    } else {
+#pragma unroll
+      for (int u = 0; u < NPB; ++u) {
+        float wv = 0.f;
+        if (COMPLETE) {
+          wv = s * gm[u];
+        } else {
+#pragma unroll
+          for (int jj = 0; jj < NE; ++jj)  // += in slot order: multi-edges sum like the CSR tile build
+            if (us[jj] == u) wv += s * gm[jj];
+        }
+        Wt[pcl * CS + u * WR + pv] = wv;
       }
-      Wt[pcl * CS + u * WR + pv] = wv;
     }
     if (!COMPLETE && pcl == 0) {
 #pragma unroll
@@ -1982,7 +2017,8 @@ __global__ void __launch_bounds__(kBlock) film_bwd_mfma(AggArgs a) {
       if (e < 0) continue;
     }
     const int64_t off = (e * a.C + cc) * 2;
-    float2 r = make_float2(s * Wt[cl * CS + v * WR + u], s * Sl[cl * SS + v]);
+    const float se = ROWS ? sv[v] : s;  // ROWS: the destination's own scale
+    float2 r = make_float2(se * Wt[cl * CS + v * WR + u], se * Sl[cl * SS + v]);
     if (a.logits) r = sigmoid_backward(r, *reinterpret_cast<const float2*>(a.gb + off));
     *reinterpret_cast<float2*>(a.dgb + off) = r;
   }
@@ -2080,10 +2116,12 @@ inline size_t lds_regular(int nt, int kmax, int cpb) {
   return (size_t)(cpb * t.SZ + cpb * nt * kmax + cpb * t.NTP + t.NTP) * sizeof(float) +
          2 * (size_t)nt * kmax * sizeof(int);
 }
-// film_bwd_mfma: Wt/D + transpose tiles + S + slot table (cpb channels of npb nodes)
+// film_bwd_mfma: Wt/D + transpose tiles + S + slot table (cpb channels of npb nodes) and, in the CSR-row
+// form (kmax == 16), the per-destination scales
 inline size_t lds_mfma(int cpb, int npb, int kmax) {
   const int cs = npb * (npb + 1) + (npb == 16 ? 4 : 2);  // film_bwd_mfma's CS, TR, SS
-  return (size_t)(cpb * cs + 4 * 16 * 40 + cpb * (npb + 1)) * sizeof(float) + 2 * (size_t)npb * kmax * sizeof(int);
+  return (size_t)(cpb * cs + 4 * 16 * 40 + cpb * (npb + 1)) * sizeof(float) + 2 * (size_t)npb * kmax * sizeof(int) +
+         (kmax == 16 ? (size_t)npb * sizeof(float) : 0);
 }
 inline size_t lds_bwd(int nt, int cpb, bool complete_logits, int lpc = 64) {
   // + the per-slot sigmoid values (float2) the COMPLETE epilogue reuses; one Gram partial per channel
@@ -2109,7 +2147,8 @@ inline bool common_args_ok(const int32_t* indptr, const int32_t* src, const int3
     if ((int64_t)num_graphs * max_nodes * (max_nodes > 0 ? max_nodes - 1 : 0) != num_edges) return false;
     return true;
   }
-  if (graph_kind != MRP_GRAPH_CSR && !MRP_GRAPH_IS_REGULAR(graph_kind)) return false;
+  // MRP_GRAPH_SIMPLE: the CSR arrays of MRP_GRAPH_CSR plus a promise the host cannot check
+  if (graph_kind != MRP_GRAPH_CSR && graph_kind != MRP_GRAPH_SIMPLE && !MRP_GRAPH_IS_REGULAR(graph_kind)) return false;
   if (MRP_GRAPH_IS_REGULAR(graph_kind) && (MRP_GRAPH_REGULAR_K(graph_kind) < 1 ||
                                           (int64_t)MRP_GRAPH_REGULAR_K(graph_kind) * num_nodes != num_edges))
     return false;
@@ -2138,5 +2177,7 @@ hipError_t dispatch_bwd_13_16(int nt, bool complete, const AggArgs& a, const Geo
 hipError_t dispatch_bwd_half_1_8(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 hipError_t dispatch_bwd_half_9_12(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
 hipError_t dispatch_bwd_half_13_16(int dtype, int nt, bool complete, const AggArgs& a, const Geometry& g, hipStream_t st);
+// film_bwd_mfma's CSR-row form (MRP_GRAPH_SIMPLE, 9..16 nodes, every dtype), film_mean_bwd_rows_mfma.hip
+hipError_t dispatch_bwd_rows_mfma(int dtype, const AggArgs& a, const Geometry& g, hipStream_t st);
 }  // namespace mrp_host
 

@@ -131,7 +131,179 @@ __global__ void __launch_bounds__(kThreads) frame_graph_build(const float* __res
   }
 }
 
+// ---------------------------------------------------------------------------
+// Range-limited / drop-out frames (mrp_frame_graph_build_range): the in-degrees differ per robot, so the
+// CSR row starts are a prefix sum over all B n destinations.  Three launches, no atomics (the sum is a
+// fixed tree: the same bits every run) and nothing read back by the host:
+//   range_rows   one thread per destination: its in-edge mask (16 bits) and every ordered pair's pose
+//                row (the complete numbering, so the encoder's rows line up whatever edges exist);
+//                the workgroup's exclusive scan of the in-degrees and its total
+//   range_blocks one workgroup: exclusive scan of the workgroup totals, and indptr's terminator
+//   range_fill   one thread per destination: its row start, src and eid from the mask
+// Workspace (int32): [nt] masks, [nt] in-workgroup prefixes, [blocks] workgroup totals / offsets.
+// ---------------------------------------------------------------------------
+constexpr int kScan = 256;
+
+// Exclusive scan of one value per thread over the workgroup (every thread calls it); total: the sum.
+__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int& total) {
+  const int i = threadIdx.x;
+  sh[i] = v;
+  __syncthreads();
+  for (int d = 1; d < kScan; d <<= 1) {
+    const int add = i >= d ? sh[i - d] : 0;
+    __syncthreads();
+    sh[i] += add;
+    __syncthreads();
+  }
+  const int incl = sh[i];
+  total = sh[kScan - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ void __launch_bounds__(kScan) range_rows(const float* __restrict__ poses,
+                                                    const uint8_t* __restrict__ active, int B, int n, int k,
+                                                    double max_range, float* __restrict__ edge_pose,
+                                                    int32_t* __restrict__ goff, int32_t* __restrict__ masks,
+                                                    int32_t* __restrict__ prefix, int32_t* __restrict__ totals) {
+  __shared__ int sh[kScan];
+  const int64_t t = (int64_t)blockIdx.x * kScan + threadIdx.x;
+  const int64_t nt = (int64_t)B * n;
+  unsigned mask = 0u;
+  if (t < nt) {
+    const int b = (int)(t / n);
+    const int v = (int)(t - (int64_t)b * n);
+    const int64_t node0 = (int64_t)b * n;
+    const float* pv = poses + t * 7;
+    if (goff != nullptr && v == 0) {
+      goff[b] = (int32_t)node0;
+      if (b == B - 1) goff[B] = (int32_t)nt;
+    }
+    const int64_t ebase = (int64_t)b * n * (n - 1);
+    const bool von = active == nullptr || active[t] != 0;
+    double d[MRP_MAX_NODES];
+    const double tvx = pv[0], tvy = pv[1], tvz = pv[2];
+    unsigned cand = 0u;  // sources in range of v
+    float rel[9];
+    for (int u = 0; u < n; ++u) {
+      if (u == v) continue;
+      const float* pu = poses + (node0 + u) * 7;
+      if (edge_pose != nullptr) {
+        relative_pose(pu, pv, rel);
+        write_pose(edge_pose, ebase + (int64_t)u * (n - 1) + (v < u ? v : v - 1), rel);
+      }
+      const double dx = __dsub_rn((double)pu[0], tvx);
+      const double dy = __dsub_rn((double)pu[1], tvy);
+      const double dz = __dsub_rn((double)pu[2], tvz);
+      d[u] = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+      const bool uon = active == nullptr || active[node0 + u] != 0;
+      if (von && uon && d[u] <= max_range) cand |= 1u << u;  // inclusive; false for a NaN distance
+    }
+    if (k > 0 && __popc(cand) > k) {
+      // the k nearest of the candidates, ties to the lower index
+      for (int j = 0; j < k; ++j) {
+        int best = -1;
+        for (int u = 0; u < n; ++u) {
+          if (!((cand >> u) & 1u) || ((mask >> u) & 1u)) continue;
+          if (best < 0 || d[u] < d[best]) best = u;
+        }
+        mask |= 1u << best;
+      }
+    } else {
+      mask = cand;
+    }
+    masks[t] = (int32_t)mask;
+  }
+  int total;
+  const int ex = block_exclusive_scan(__popc(mask), sh, total);
+  if (t < nt) prefix[t] = ex;
+  if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// One workgroup: the workgroup totals become exclusive offsets, chunk by chunk with a running carry.
+__global__ void __launch_bounds__(kScan) range_blocks(int32_t* __restrict__ totals, int nblocks,
+                                                      int32_t* __restrict__ indptr, int64_t nt) {
+  __shared__ int sh[kScan];
+  int carry = 0;
+  for (int base = 0; base < nblocks; base += kScan) {
+    const int i = base + (int)threadIdx.x;
+    const int v = i < nblocks ? totals[i] : 0;
+    int total;
+    const int ex = block_exclusive_scan(v, sh, total);
+    if (i < nblocks) totals[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0 && indptr != nullptr) indptr[nt] = carry;
+}
+
+__global__ void __launch_bounds__(kScan) range_fill(int B, int n, const int32_t* __restrict__ masks,
+                                                    const int32_t* __restrict__ prefix,
+                                                    const int32_t* __restrict__ offsets, int32_t* __restrict__ indptr,
+                                                    int32_t* __restrict__ src, int32_t* __restrict__ eid) {
+  const int64_t t = (int64_t)blockIdx.x * kScan + threadIdx.x;
+  const int64_t nt = (int64_t)B * n;
+  if (t >= nt) return;
+  const int b = (int)(t / n);
+  const int v = (int)(t - (int64_t)b * n);
+  const int64_t node0 = (int64_t)b * n;
+  const int64_t ebase = (int64_t)b * n * (n - 1);
+  const unsigned mask = (unsigned)masks[t];
+  int row = offsets[blockIdx.x] + prefix[t];
+  if (indptr != nullptr) indptr[t] = row;
+  for (int u = 0; u < n; ++u) {
+    if (!((mask >> u) & 1u)) continue;
+    if (src != nullptr) src[row] = (int32_t)(node0 + u);
+    if (eid != nullptr) eid[row] = (int32_t)(ebase + (int64_t)u * (n - 1) + (v < u ? v : v - 1));
+    ++row;
+  }
+}
+
 }  // namespace mrp_graph
+
+extern "C" int64_t mrp_frame_graph_build_range_workspace(int32_t num_graphs, int32_t n) {
+  if (num_graphs <= 0 || n <= 0) return 0;
+  const int64_t nt = (int64_t)num_graphs * n;
+  const int64_t blocks = (nt + mrp_graph::kScan - 1) / mrp_graph::kScan;
+  return (2 * nt + blocks) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int mrp_frame_graph_build_range(const float* poses, const uint8_t* active, int32_t num_graphs, int32_t n,
+                                           int32_t knn_k, double max_range, float* edge_pose, int32_t* indptr,
+                                           int32_t* src, int32_t* eid, int32_t* graph_off, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  if (num_graphs < 0 || n < 0 || n > MRP_MAX_NODES || knn_k < 0) return hipErrorInvalidValue;
+  if (knn_k > 0 && knn_k >= n) return hipErrorInvalidValue;
+  if (!(max_range >= 0.0)) return hipErrorInvalidValue;  // negative or NaN
+  const int64_t nt = (int64_t)num_graphs * n;
+  const int64_t ne = nt * (n > 0 ? n - 1 : 0);
+  if (nt >= 0x7fffffff || ne >= 0x7fffffff) return hipErrorInvalidValue;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (nt == 0) {
+    if (graph_off != nullptr) {
+      hipError_t e = hipMemsetAsync(graph_off, 0, sizeof(int32_t) * ((size_t)num_graphs + 1), st);
+      if (e != hipSuccess) return e;
+    }
+    if (indptr != nullptr) return hipMemsetAsync(indptr, 0, sizeof(int32_t), st);
+    return hipSuccess;
+  }
+  if (poses == nullptr || workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 3u) != 0 ||
+      workspace_bytes < mrp_frame_graph_build_range_workspace(num_graphs, n))
+    return hipErrorInvalidValue;
+  const int blocks = (int)((nt + mrp_graph::kScan - 1) / mrp_graph::kScan);
+  int32_t* masks = static_cast<int32_t*>(workspace);
+  int32_t* prefix = masks + nt;
+  int32_t* totals = prefix + nt;
+  hipLaunchKernelGGL(mrp_graph::range_rows, dim3((unsigned)blocks), dim3(mrp_graph::kScan), 0, st, poses, active,
+                     (int)num_graphs, (int)n, (int)knn_k, max_range, edge_pose, graph_off, masks, prefix, totals);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mrp_graph::range_blocks, dim3(1), dim3(mrp_graph::kScan), 0, st, totals, blocks, indptr, nt);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mrp_graph::range_fill, dim3((unsigned)blocks), dim3(mrp_graph::kScan), 0, st, (int)num_graphs,
+                     (int)n, masks, prefix, totals, indptr, src, eid);
+  return hipGetLastError();
+}
 
 extern "C" int mrp_frame_graph_build(const float* poses, int32_t num_graphs, int32_t n, int32_t knn_k,
                                      float* edge_pose, int32_t* indptr, int32_t* src, int32_t* eid,

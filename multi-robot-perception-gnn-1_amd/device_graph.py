@@ -29,13 +29,20 @@ def _complete_host_edges(B: int, n: int):
     return (cs[None] + off).reshape(-1), (cd[None] + off).reshape(-1)
 
 
-def frame_batch(poses: torch.Tensor, knn: Optional[int] = None, stream=None) -> RobotGraph:
+def frame_batch(poses: torch.Tensor, knn: Optional[int] = None, max_range: Optional[float] = None,
+                active: Optional[torch.Tensor] = None, stream=None) -> RobotGraph:
     """A batch of per-frame graphs built on the device.
 
     ``poses``: (B, n, 7) float32 CUDA tensor, rows ``(tx, ty, tz, qx, qy, qz, qw)``; n <= 16.
     ``knn=None``: the reference's complete graphs (edge order of ``dgl.batch`` over
     ``dgl/dataloader.py:88-95`` frames); ``knn=k``: k-NN(k) graphs (edges destination-major,
     sources ascending, as :func:`graph.knn_edges`).  Sets ``edata['pose']`` (E, 9) on the device.
+
+    ``max_range`` (float, ``inf``: unlimited) and / or ``active`` ((B, n) CUDA bool tensor: the robots that
+    take part): range-limited / drop-out frames by ``mrp_frame_graph_build_range`` — the rule and the
+    result of :func:`graph.frame_graph` with the same arguments, batched: every robot stays a node, the
+    B n (n-1) edge slots and pose rows are the complete frames', ``csr()`` lists the existing edges under
+    ``GRAPH_SIMPLE``.  No host synchronisation: the build can be captured in a HIP graph.
     """
     if not poses.is_cuda:
         raise RuntimeError("frame_batch builds graphs on the GPU; use graph.frame_graph + graph.batch on the host")
@@ -49,6 +56,8 @@ def frame_batch(poses: torch.Tensor, knn: Optional[int] = None, stream=None) -> 
         raise ValueError(f"knn={k} needs 1 <= k < n={n}")
     poses = poses.detach().to(torch.float32).contiguous()
     dev = poses.device
+    if max_range is not None or active is not None:
+        return _frame_batch_range(poses, B, n, k, max_range, active, stream)
     nt = B * n
     ne = nt * k if k else nt * max(n - 1, 0)
     i32 = dict(dtype=torch.int32, device=dev)
@@ -78,5 +87,46 @@ def frame_batch(poses: torch.Tensor, knn: Optional[int] = None, stream=None) -> 
     g._csr_cache.setdefault((str(dev), _lib.GRAPH_CSR), csr._replace(graph_kind=_lib.GRAPH_CSR))
     if 1 <= kdeg <= _lib.MAX_REGULAR_K:
         g._csr_cache.setdefault((str(dev), _lib.graph_regular(kdeg)), csr._replace(graph_kind=_lib.graph_regular(kdeg)))
+    g.edata["pose"] = edge_pose
+    return g
+
+
+def _frame_batch_range(poses: torch.Tensor, B: int, n: int, k: int, max_range, active, stream) -> RobotGraph:
+    dev = poses.device
+    rng = float("inf") if max_range is None else float(max_range)
+    if not rng >= 0.0:
+        raise ValueError(f"max_range={max_range} must be >= 0 (inf: unlimited)")
+    if active is not None:
+        if not active.is_cuda or active.dtype != torch.bool or tuple(active.shape) != (B, n):
+            raise ValueError(f"active must be a CUDA bool tensor of shape {(B, n)}")
+        active = active.contiguous()
+    nt, ne = B * n, B * n * max(n - 1, 0)
+    i32 = dict(dtype=torch.int32, device=dev)
+    lib = _lib.load_library()
+    nbytes = int(lib.mrp_frame_graph_build_range_workspace(B, n))
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):  # the zero fills below run on the build's stream
+        edge_pose = torch.empty(ne, 9, dtype=torch.float32, device=dev)
+        indptr = torch.empty(nt + 1, **i32)
+        # capacity = every slot; the tail past indptr[-1] is never read (zeroed so the arrays hold no garbage)
+        src = torch.zeros(ne, **i32)
+        eid = torch.zeros(ne, **i32)
+        goff = torch.empty(B + 1, **i32)
+        ws = torch.empty(max(nbytes // 4, 1), **i32)
+        _lib.check(lib.mrp_frame_graph_build_range(poses.data_ptr(), active.data_ptr() if active is not None else None,
+                                                   B, n, k, rng, edge_pose.data_ptr(), indptr.data_ptr(),
+                                                   src.data_ptr(), eid.data_ptr(), goff.data_ptr(), ws.data_ptr(),
+                                                   nbytes, s.cuda_stream),
+                   "mrp_frame_graph_build_range")
+    csr = GraphCSR(indptr, src, eid, goff, B, n, nt, ne, _lib.GRAPH_SIMPLE, True)
+
+    def edge_active():  # one device-to-host copy, only if the host asks
+        mask = np.zeros(ne, dtype=bool)
+        mask[eid.cpu().numpy()[:int(indptr[-1].item())]] = True
+        return mask
+
+    g = RobotGraph._from_device(lambda: _complete_host_edges(B, n), nt, ne, [n] * B, [ne // B if B else 0] * B,
+                                csr=csr, device=dev, complete=False, kdeg=0, edge_active_fn=edge_active)
+    g._csr_cache[(str(dev), _lib.GRAPH_CSR)] = csr._replace(graph_kind=_lib.GRAPH_CSR)
     g.edata["pose"] = edge_pose
     return g

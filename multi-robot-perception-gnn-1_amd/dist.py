@@ -69,6 +69,9 @@ def shard_graph(g, rank: int, world: int):
 
     from .graph import RobotGraph
     lo, hi = shard_range(g.batch_size, rank, world)
+    if g._masked():
+        raise ValueError("shard_graph: a graph with an edge_active mask (range-limited / drop-out frames) "
+                         "cannot be sharded yet; shard the poses and build each rank's frames")
     bnn = [int(v) for v in g.batch_num_nodes().tolist()]
     bne = [int(v) for v in g.batch_num_edges().tolist()]
     noff = np.concatenate([[0], np.cumsum(bnn)]).astype(np.int64)

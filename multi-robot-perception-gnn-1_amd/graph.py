@@ -25,7 +25,7 @@ from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import GRAPH_COMPLETE, GRAPH_CSR, MAX_NODES, MAX_REGULAR_K, graph_regular
+from ._lib import GRAPH_COMPLETE, GRAPH_CSR, GRAPH_SIMPLE, MAX_NODES, MAX_REGULAR_K, graph_regular
 from .pose import relative_pose_batch
 
 
@@ -40,7 +40,11 @@ class GraphCSR(NamedTuple):
     max_nodes: int
     num_nodes: int
     num_edges: int
-    graph_kind: int  # GRAPH_COMPLETE (reference topology, arithmetic edge ids), graph_regular(k) or GRAPH_CSR
+    # GRAPH_COMPLETE (reference topology, arithmetic edge ids), graph_regular(k), GRAPH_CSR, or GRAPH_SIMPLE:
+    # no two entries share (source, destination); num_edges is then the number of gamma/beta rows (edge
+    # slots), src / eid have that capacity and list only the existing edges (indptr[-1] of them)
+    graph_kind: int
+    sparse_eid: bool = False  # the edge ids may leave gamma/beta rows unnamed (a masked graph's arrays)
 
 
 class _FeatureDict(dict):
@@ -71,6 +75,7 @@ class RobotGraph:
         num_nodes: Optional[int] = None,
         batch_num_nodes: Optional[Sequence[int]] = None,
         batch_num_edges: Optional[Sequence[int]] = None,
+        edge_active=None,
     ):
         src_t = torch.as_tensor(np.asarray(src), dtype=torch.int64).reshape(-1).cpu()
         dst_t = torch.as_tensor(np.asarray(dst), dtype=torch.int64).reshape(-1).cpu()
@@ -94,13 +99,21 @@ class RobotGraph:
         self.edata: Dict[str, torch.Tensor] = _FeatureDict(src_t.numel(), "edata")
         self._csr_cache: Dict[str, GraphCSR] = {}
         self._host_csr = None
+        self._edge_active = None
+        self._edge_active_fn = None
+        if edge_active is not None:
+            m = torch.as_tensor(edge_active).reshape(-1).cpu()
+            if m.dtype != torch.bool or m.numel() != self._ne:
+                raise ValueError(f"edge_active must be a bool tensor of {self._ne} entries")
+            self._edge_active = m
 
     @classmethod
     def _from_device(cls, edge_fn, num_nodes: int, num_edges: int, bnn: Sequence[int], bne: Sequence[int],
                      csr: Optional[GraphCSR] = None, device=None, complete: Optional[bool] = None,
-                     kdeg: Optional[int] = None) -> "RobotGraph":
+                     kdeg: Optional[int] = None, edge_active_fn=None) -> "RobotGraph":
         """A graph whose structure was built on the device (``frame_batch``): the host edge list is
-        produced by ``edge_fn()`` only if something asks for it (``edges()``, ``host_csr()``)."""
+        produced by ``edge_fn()`` only if something asks for it (``edges()``, ``host_csr()``); likewise the
+        mask of a range-limited graph by ``edge_active_fn()``."""
         g = cls.__new__(cls)
         g._edge_store = None
         g._edge_fn = edge_fn
@@ -115,6 +128,8 @@ class RobotGraph:
         g._host_csr = None
         g._complete = complete
         g._kdeg = kdeg
+        g._edge_active = None
+        g._edge_active_fn = edge_active_fn
         return g
 
     @property
@@ -131,6 +146,18 @@ class RobotGraph:
             self._edge_store = (torch.as_tensor(src, dtype=torch.int64).cpu(),
                                 torch.as_tensor(dst, dtype=torch.int64).cpu())
         return self._edge_store
+
+    @property
+    def edge_active(self) -> Optional[torch.Tensor]:
+        """Bool host tensor over the E edge slots, or None when every edge exists (every graph but the
+        range-limited / drop-out ones of ``frame_graph`` / ``frame_batch``).  Pose rows, encoder outputs and
+        ``edges()`` cover all slots; ``in_degrees``, ``host_csr`` and ``csr`` only the active ones."""
+        if self._edge_active is None and self._edge_active_fn is not None:
+            self._edge_active = torch.as_tensor(self._edge_active_fn(), dtype=torch.bool).reshape(-1).cpu()
+        return self._edge_active
+
+    def _masked(self) -> bool:
+        return self._edge_active is not None or self._edge_active_fn is not None
 
     # ----------------------------------------------------------------- DGL-like API
     def num_nodes(self) -> int:
@@ -154,7 +181,8 @@ class RobotGraph:
         return self._src, self._dst
 
     def in_degrees(self) -> torch.Tensor:
-        return torch.bincount(self._dst, minlength=self._num_nodes)
+        dst = self._dst[self.edge_active] if self._masked() else self._dst
+        return torch.bincount(dst, minlength=self._num_nodes)
 
     @property
     def device(self) -> torch.device:
@@ -192,6 +220,7 @@ class RobotGraph:
         g._host_csr = self._host_csr
         g._complete = getattr(self, "_complete", None)
         g._kdeg = getattr(self, "_kdeg", None)
+        g._edge_active, g._edge_active_fn = self._edge_active, self._edge_active_fn
         return g
 
     def cuda(self, device=None) -> "RobotGraph":
@@ -201,13 +230,22 @@ class RobotGraph:
     def host_csr(self):
         """int32 numpy CSR by destination, validated: (indptr, src, eid, graph_off, max_nodes)."""
         if self._host_csr is None:
-            self._host_csr = build_csr(self._src.numpy(), self._dst.numpy(), self._num_nodes, self._bnn)
+            if self._masked():
+                # the active edges only; eid = the edge slot (row of the gamma/beta tensor)
+                slot = np.nonzero(self.edge_active.numpy())[0]
+                indptr, src, order, goff, mx = build_csr(self._src.numpy()[slot], self._dst.numpy()[slot],
+                                                         self._num_nodes, self._bnn)
+                self._host_csr = (indptr, src, slot[order].astype(np.int32), goff, mx)
+            else:
+                self._host_csr = build_csr(self._src.numpy(), self._dst.numpy(), self._num_nodes, self._bnn)
         return self._host_csr
 
     def is_complete(self) -> bool:
         """True when every graph of the batch is the reference's complete graph over the same
         number of robots with edges in ``complete_edges`` order (``dgl/dataloader.py:88-95``);
         the kernels then compute edge ids arithmetically instead of walking the CSR."""
+        if self._masked():
+            return False
         if getattr(self, "_complete", None) is None:
             self._complete = is_complete_batch(self._src.numpy(), self._dst.numpy(), self._bnn)
         return self._complete
@@ -219,11 +257,15 @@ class RobotGraph:
             self._kdeg = int(deg[0]) if deg.size and deg[0] > 0 and np.all(deg == deg[0]) else 0
         return self._kdeg
 
-    def csr(self, device, allow_complete: bool = True, allow_regular: bool = True) -> GraphCSR:
+    def csr(self, device, allow_complete: bool = True, allow_regular: bool = True, simple: bool = True) -> GraphCSR:
         """Device CSR for the kernels.  ``graph_kind`` is GRAPH_COMPLETE for the reference topology,
         ``graph_regular(k)`` when every node has k in-edges (k <= 8; the backward then keeps one
-        Gram accumulator per edge), else GRAPH_CSR."""
+        Gram accumulator per edge), else GRAPH_CSR.  A graph with an ``edge_active`` mask gives GRAPH_SIMPLE
+        over its active edges (``num_edges`` = all E slots, ``eid`` = the slot), or with ``simple=False`` the
+        same arrays as GRAPH_CSR (``sparse_eid`` set: the caller clears the gradient rows no edge names)."""
         device = torch.device(device)
+        if self._masked():
+            return self._masked_csr(device, GRAPH_SIMPLE if simple else GRAPH_CSR)
         if allow_complete and self.is_complete():
             kind = GRAPH_COMPLETE
         elif allow_regular and 1 <= self.in_degree_k() <= MAX_REGULAR_K:
@@ -239,6 +281,24 @@ class RobotGraph:
         csr = GraphCSR(to(indptr), to(src), to(eid), to(goff), len(self._bnn), max_nodes,
                        self._num_nodes, self.num_edges(), kind)
         self._csr_cache[key] = csr
+        return csr
+
+    def _masked_csr(self, device: torch.device, kind: int) -> GraphCSR:
+        hit = self._csr_cache.get((str(device), kind))
+        if hit is not None:
+            return hit
+        other = self._csr_cache.get((str(device), GRAPH_CSR if kind == GRAPH_SIMPLE else GRAPH_SIMPLE))
+        if other is not None:
+            csr = other._replace(graph_kind=kind)
+        else:
+            indptr, src, eid, goff, max_nodes = self.host_csr()
+            E = self.num_edges()
+            # src / eid padded to the slot count (never empty where gamma/beta rows exist)
+            pad = lambda a: np.concatenate([a, np.zeros(E - a.shape[0], np.int32)])  # noqa: E731
+            to = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+            csr = GraphCSR(to(indptr), to(pad(src)), to(pad(eid)), to(goff), len(self._bnn), max_nodes,
+                           self._num_nodes, E, kind, True)
+        self._csr_cache[(str(device), kind)] = csr
         return csr
 
     def __repr__(self) -> str:
@@ -332,14 +392,54 @@ def knn_edges(positions, k: int):
     return src, dst
 
 
-def frame_graph(poses, knn: Optional[int] = None) -> RobotGraph:
+def range_adjacency(positions, max_range: Optional[float] = None, active=None, knn: Optional[int] = None):
+    """(n, n) bool ``adj[u, v]``: edge u->v of a range-limited / drop-out frame.  It exists iff u != v,
+    both robots are active and ``d(u, v) <= max_range`` (inclusive, float64, ``sqrt((dx^2 + dy^2) + dz^2)``;
+    a NaN distance gives no edge; ``None`` or ``inf``: unlimited); with ``knn=k`` each destination keeps at
+    most the k nearest of those, ties to the lower index.  The rule of ``mrp_frame_graph_build_range``."""
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    n = pos.shape[0]
+    rng = np.inf if max_range is None else float(max_range)
+    if not rng >= 0.0:
+        raise ValueError(f"max_range={max_range} must be >= 0 (inf: unlimited)")
+    k = 0 if knn is None else int(knn)
+    if knn is not None and not 1 <= k < n:
+        raise ValueError(f"knn={k} needs 1 <= k < n={n}")
+    act = np.ones(n, bool) if active is None else np.asarray(active).astype(bool).reshape(-1)
+    if act.shape[0] != n:
+        raise ValueError(f"active must have {n} entries")
+    diff = pos[:, None, :] - pos[None, :, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.sqrt((diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2])
+        adj = (d <= rng) & act[:, None] & act[None, :] & ~np.eye(n, dtype=bool)
+    if k:
+        for v in range(n):
+            cand = [u for u in range(n) if adj[u, v]]
+            if len(cand) > k:
+                cand.sort(key=lambda u: (d[u, v], u))
+                adj[:, v] = False
+                adj[cand[:k], v] = True
+    return adj
+
+
+def frame_graph(poses, knn: Optional[int] = None, max_range: Optional[float] = None, active=None) -> RobotGraph:
     """One frame: nodes = robots, ``edata['pose']`` = relative pose of every edge
     (``dgl/dataloader.py:97-122``).  ``poses``: (n, 7) ``(t, q_xyzw)``; complete graph unless
-    ``knn`` is given."""
+    ``knn`` is given.
+
+    With ``max_range`` and / or ``active`` ((n,) bool: robots that take part) the frame is range-limited:
+    all n robots stay nodes, the n(n-1) edge slots and their pose rows are the complete frame's, and
+    ``edge_active`` marks the edges of :func:`range_adjacency` (``knn`` then caps each in-degree)."""
     poses = np.asarray(poses)
     n = poses.shape[0]
-    src, dst = complete_edges(n) if knn is None else knn_edges(poses[:, :3], knn)
-    g = RobotGraph(src, dst, num_nodes=n)
+    if max_range is not None or active is not None:
+        src, dst = complete_edges(n)
+        adj = range_adjacency(poses[:, :3], max_range, active, knn)
+        mask = adj[np.asarray(src, np.int64), np.asarray(dst, np.int64)] if len(src) else np.zeros(0, bool)
+        g = RobotGraph(src, dst, num_nodes=n, edge_active=torch.from_numpy(np.ascontiguousarray(mask)))
+    else:
+        src, dst = complete_edges(n) if knn is None else knn_edges(poses[:, :3], knn)
+        g = RobotGraph(src, dst, num_nodes=n)
     if len(src):
         rel = relative_pose_batch(poses[np.asarray(src)], poses[np.asarray(dst)])
     else:
@@ -354,16 +454,20 @@ def batch(graphs: Iterable[RobotGraph]) -> RobotGraph:
     graphs: List[RobotGraph] = list(graphs)
     if not graphs:
         raise ValueError("batch() needs at least one graph")
-    srcs, dsts, bnn, bne = [], [], [], []
+    srcs, dsts, bnn, bne, masks = [], [], [], [], []
+    masked = any(g._masked() for g in graphs)  # then the union is masked: an unmasked part's edges all exist
     off = 0
     for g in graphs:
         s, d = g.edges()
         srcs.append(s + off)
         dsts.append(d + off)
+        if masked:
+            masks.append(g.edge_active if g._masked() else torch.ones(s.numel(), dtype=torch.bool))
         bnn.extend(g._bnn)
         bne.extend(g._bne)
         off += g.num_nodes()
-    out = RobotGraph(torch.cat(srcs), torch.cat(dsts), num_nodes=off, batch_num_nodes=bnn, batch_num_edges=bne)
+    out = RobotGraph(torch.cat(srcs), torch.cat(dsts), num_nodes=off, batch_num_nodes=bnn, batch_num_edges=bne,
+                     edge_active=torch.cat(masks) if masked else None)
     for key in graphs[0].ndata:
         if all(key in g.ndata for g in graphs):
             out.ndata[key] = torch.cat([g.ndata[key] for g in graphs], 0)
@@ -390,7 +494,8 @@ def unbatch(g: RobotGraph) -> List[RobotGraph]:
         s, d = src[e0:e1] - n0, dst[e0:e1] - n0
         if s.size and (s.min() < 0 or d.min() < 0 or s.max() >= n1 - n0 or d.max() >= n1 - n0):
             raise ValueError(f"graph {i}: its edges leave its node range (not a dgl.batch result)")
-        gi = RobotGraph(s, d, num_nodes=int(n1 - n0))
+        gi = RobotGraph(s, d, num_nodes=int(n1 - n0),
+                        edge_active=g.edge_active[e0:e1].clone() if g._masked() else None)
         for k, v in g.ndata.items():
             gi.ndata[k] = v[n0:n1]
         for k, v in g.edata.items():
@@ -415,6 +520,9 @@ def save_graphs(filename: str, g_list, labels: Optional[Dict[str, torch.Tensor]]
     arrays = {"magic": np.array(_CACHE_MAGIC), "num_graphs": np.array(len(g_list), np.int64)}
     if g_list:
         b = batch(g_list)
+        if b._masked():
+            raise ValueError("save_graphs: a graph with an edge_active mask (range-limited / drop-out frame) "
+                             "cannot be saved: the cache format has no field for the mask")
         src, dst = (t.numpy() for t in b.edges())
         arrays.update(src=src, dst=dst, bnn=np.asarray(b._bnn, np.int64), bne=np.asarray(b._bne, np.int64))
         for k, v in b.ndata.items():

@@ -388,6 +388,83 @@ int64_t mrp_film_mean_bwd_cl_workspace(int32_t num_graphs, int32_t max_nodes, in
                                        int32_t C, int32_t P, int32_t mode, int32_t want_grad_gb);
 
 /*
+ * The max-pooled FiLM aggregation (ABI 22, extended): node_udf = torch.max(mailbox, 1) in place of the
+ * reference's torch.mean(mailbox, 1) (dgl/model/models.py:207-208).  An operator of its own: it is not a
+ * value of enum mrp_agg_mode, and every mrp_film_mean_* entry point keeps rejecting mode 3.
+ *
+ * For destination v with CSR row [indptr[v], indptr[v+1]), entries j = 0, 1, ... in row order (edge-id
+ * order, DGL's mailbox order), e_j the entry's edge id and u_j its source:
+ *
+ *   m_j[c,p]       = fl(fl(gamma_{e_j}[c] * x[u_j,c,p]) + beta_{e_j}[c])     no FMA contraction
+ *   out[v,c,p]     = max_j m_j[c,p]                                          zeros when the row is empty
+ *   w(v,c,p)       = the smallest j attaining that max                       the first maximal entry
+ *   grad_x[u,c,p]  = sum over (v, j) with u_j = u of gamma_{e_j}[c] * sel_j(v,c,p)   (+ grad_x_base[u,c,p])
+ *   grad_gb[e,c,0] = sum_p x[u,c,p] * sel_{j(e)}(v,c,p)
+ *   grad_gb[e,c,1] = sum_p sel_{j(e)}(v,c,p)
+ *   sel_j(v,c,p)   = grad_out[v,c,p] if j = w(v,c,p), else an exact 0
+ *
+ * which is torch.max(mailbox, 1) and its autograd.  Ties and NaN: on a tie the first maximal entry takes
+ * the whole gradient (it is not split); a NaN message beats every number and the first NaN wins (torch's
+ * update: a message replaces the running maximum unless it is <= it, and nothing replaces a NaN).  The
+ * backward stores no argmax; it recomputes w from x, gamma and beta with the forward's own arithmetic.
+ * With MRP_AGG_GB_LOGITS gamma/beta = sigmoid(z) formed in the kernel and grad_gb is d z, as for the mean.
+ *
+ * Every CSR entry is its own message: parallel edges u->v with different (gamma, beta) are two candidates,
+ * and self-loops are allowed, under every graph kind (MRP_GRAPH_SIMPLE's promise is not needed here).
+ * Every grad_gb row that no CSR entry names is written as zeros, for every graph kind; an entry that
+ * never wins gets exact zeros (finite operands).  A node of in-degree 0 gets out = 0 and contributes
+ * nothing to any gradient.
+ *
+ * Precondition, not checked on the device: every in-degree is <= MRP_FILM_MAX_DEGREE (a complete 16-node
+ * graph has 15, with self-loops 16); MRP_GRAPH_REGULAR(k) with k above it is declined.
+ *
+ * 16-bit features: widened exactly on load, the fp32 arithmetic above unchanged, one round-to-nearest-even
+ * at each store; gamma, beta and grad_gb stay fp32:  mrp_film_max_fwd(T, x) == T(mrp_film_max_fwd(float(x)))
+ * bit for bit, likewise grad_x (on grad_out, x and grad_x_base widened) and grad_gb whenever the fp32 sums
+ * are exact.
+ *
+ * Determinism: no atomics, one writer per output element, every sum in a fixed order.
+ *
+ * Non-finite values: max selects, it does not mix, so an input NaN or infinity is confined to its own
+ * (destination, channel, pixel) of `out` — stricter than the mean backward's per-graph promise above.  In
+ * the backward a slot that loses contributes gamma * 0, x * 0 and 0, as autograd does: a non-finite gamma
+ * or x of a losing slot still reaches grad_x[u,c,p] / grad_gb[e,c,0] of that slot (0 * inf = NaN), and
+ * nothing else.
+ *
+ * flags: 0 or MRP_AGG_GB_LOGITS.  grad_x or grad_gb may each be NULL to skip that output; with both NULL
+ * the backward returns success without a launch.  Validation precedes any launch and matches the typed
+ * mean entry points (sizes, strides, max_nodes > MRP_MAX_NODES, unknown kind, dtype or flags, inconsistent
+ * COMPLETE counts, NULL pointers where there is work); empty work returns success.  No allocation, no
+ * host synchronisation, capturable (a hipMemsetAsync of grad_gb precedes the kernels of non-COMPLETE
+ * graphs).  out_node_stride / g_node_stride let the aggregate and its gradient be the second half of a
+ * concatenation buffer, as above.
+ */
+#define MRP_FILM_MAX_DEGREE 16
+
+int mrp_film_max_fwd(int32_t dtype,
+                     const void* x, int64_t x_node_stride,
+                     const float* gb,
+                     const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                     const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                     int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                     int32_t C, int32_t P, int32_t flags,
+                     void* out, int64_t out_node_stride,
+                     void* stream);
+
+int mrp_film_max_bwd(int32_t dtype,
+                     const void* grad_out, int64_t g_node_stride,
+                     const void* x, int64_t x_node_stride,
+                     const float* gb,
+                     const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                     const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                     int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                     int32_t C, int32_t P, int32_t flags,
+                     void* grad_x, int64_t gx_node_stride,
+                     const void* grad_x_base, int64_t base_node_stride,
+                     float* grad_gb,
+                     void* stream);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

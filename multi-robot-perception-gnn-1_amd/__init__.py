@@ -10,6 +10,8 @@ from ._lib import MAX_NODES, MAX_REGULAR_K, MODES, graph_regular, load_library  
 from .aggregate import (EpilogueSpec, FilmMeanFunction, film_mean, film_mean_cat,  # noqa: F401
                         film_mean_cat_forward_into, film_mean_forward_into, film_mean_mix, film_mean_residual,
                         pixel_strides, set_channels_last)
+from .aggregate import (FilmMaxFunction, film_max, film_max_backward, film_max_cat,  # noqa: F401
+                        film_max_forward_into)
 from . import compat, compress, encoder  # noqa: F401
 from .compress import compress_precision, compress_precision_scope, set_compress_precision  # noqa: F401
 from .compress import channels_last_compress_fp32, set_channels_last_compress_fp32  # noqa: F401

@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_fwd_cl",
     "mrp_film_mean_bwd_cl",
     "mrp_film_mean_bwd_cl_workspace",
+    "mrp_film_max_fwd",
+    "mrp_film_max_bwd",
     "mrp_compress_fwd",
     "mrp_compress_weight_transpose",
     "mrp_compress_bwd_data",
@@ -88,6 +90,7 @@ EXPORTED_SYMBOLS = (
 )
 ABI_VERSION = 22
 MAX_NODES = 16
+FILM_MAX_DEGREE = 16  # MRP_FILM_MAX_DEGREE: largest in-degree of the max-pooled aggregation
 
 HIP_ERROR_NOT_SUPPORTED = 801  # hipErrorNotSupported: a fused path declines this shape
 
@@ -184,6 +187,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_mean_bwd_cl.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_cl_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32, _I32, _I32]
     lib.mrp_film_mean_bwd_cl_workspace.restype = ctypes.c_int64
+    # the max-pooled aggregation: `flags` (0 or GB_LOGITS) sits where the mean's `mode` does
+    lib.mrp_film_max_fwd.argtypes = [_I32, _P, _I64, _P] + graph + [_P, _I64, _P]
+    lib.mrp_film_max_fwd.restype = ctypes.c_int
+    lib.mrp_film_max_bwd.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, _P]
+    lib.mrp_film_max_bwd.restype = ctypes.c_int
     lib.mrp_tuning_set.argtypes = [ctypes.c_char_p, _I32]
     lib.mrp_tuning_set.restype = ctypes.c_int
     lib.mrp_compress_fwd.argtypes = [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]

@@ -558,3 +558,197 @@ def film_mean_cat(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, mo
     if (m & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN:
         gb = None
     return FilmMeanCatFunction.apply(x, gb, csr, m)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Max-pooled FiLM aggregation: ``node_udf = torch.max(mailbox, 1)`` (``mrp_film_max_fwd`` / ``_bwd``).
+#
+#     m_j   = gamma_e * x[src(e)] + beta_e          for v's in-edges e in edge-id (mailbox) order
+#     out_v = max_j m_j                             element-wise; zeros if deg v = 0
+#
+# and torch's autograd of it: on a tie the first maximal message takes the whole gradient, a NaN message
+# beats every number and the first NaN wins.  An operator of its own, not a value of ``_lib.MODES`` (that
+# table numbers the ``mode`` argument of ``mrp_film_mean_*``).  Every CSR entry is its own candidate, so
+# parallel edges and self-loops are meaningful; every in-degree must be <= ``_lib.FILM_MAX_DEGREE``.
+# channels_last features take the copy-first route: copied to NCHW, aggregated by the NCHW kernels.
+# ---------------------------------------------------------------------------------------------------------
+def _check_max_degree(csr: GraphCSR) -> None:
+    bound = getattr(csr, "max_in_degree", -1)
+    if bound < 0:
+        raise ValueError("film_max needs the graph's in-degree bound: GraphCSR.max_in_degree is unknown (-1); "
+                         f"every in-degree must be <= {_lib.FILM_MAX_DEGREE}")
+    if bound > _lib.FILM_MAX_DEGREE:
+        raise ValueError(f"film_max: a node has in-degree {bound}; the limit is {_lib.FILM_MAX_DEGREE} "
+                         "(MRP_FILM_MAX_DEGREE)")
+
+
+def _max_gb(gb, csr, C):
+    if gb is None:
+        raise ValueError("gamma/beta tensor required for film_max")
+    gb = gb.reshape(csr.num_edges, C, 2)
+    if not gb.is_contiguous() or gb.dtype != torch.float32:
+        gb = gb.contiguous().float()
+    _require_device(gb)
+    return gb
+
+
+def _check_max_flags(flags: int) -> int:
+    flags = int(flags)
+    if flags not in (0, _lib.GB_LOGITS):
+        raise ValueError(f"film_max flags must be 0 or GB_LOGITS ({_lib.GB_LOGITS:#x}), got {flags:#x}")
+    return flags
+
+
+def film_max_forward_into(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, flags: int,
+                          out: torch.Tensor) -> torch.Tensor:
+    """Run ``mrp_film_max_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
+    half of a ``torch.cat((h, g_h), 1)`` buffer.  ``flags``: 0 or ``_lib.GB_LOGITS``.  No autograd."""
+    _check_max_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _require_device(x, out)
+    flags = _check_max_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
+    os_ = node_stride(out)
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    gb = _max_gb(gb, csr, C)
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_max_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *_graph_args(gb, csr, C, H * W, flags),
+                                    _ptr(out), os_, _stream(x.device))
+    _lib.check(code, "mrp_film_max_fwd")
+    PATH_COUNTS["max_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+    return out
+
+
+def film_max_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, flags: int,
+                      need_dx: bool, need_dgb: bool, grad_x_base: Optional[torch.Tensor] = None):
+    """(grad_x or None, grad_gb (E, C, 2) or None) of :func:`film_max_forward_into`; ``grad_x_base``
+    (N, C, H, W), if given, is added into grad_x by the kernel.  The winners are recomputed from x and gb
+    (no argmax is saved); grad_x is NCHW in x's dtype, grad_gb fp32 with every unnamed row zero."""
+    _check_max_degree(csr)
+    _require_device(grad_out, x)
+    flags = _check_max_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    # the kernel reads grad_out and the base with x's extents: a mismatch would be an out-of-bounds read
+    if tuple(grad_out.shape) != (n, C, H, W):
+        raise ValueError(f"grad_out must be {(n, C, H, W)}, got {tuple(grad_out.shape)}")
+    if grad_x_base is not None and tuple(grad_x_base.shape) != (n, C, H, W):
+        raise ValueError(f"grad_x_base must be {(n, C, H, W)}, got {tuple(grad_x_base.shape)}")
+    if grad_x_base is not None:
+        _require_device(grad_x_base)
+    dtype = x.dtype
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
+    grad_out, gs = _as_node_major(grad_out)
+    x, xs = _as_node_major(x)
+    bs = 0
+    if grad_x_base is not None and need_dx:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
+        grad_x_base, bs = _as_node_major(grad_x_base)
+    else:
+        grad_x_base = None
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
+    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    if not (need_dx or need_dgb):
+        return None, None
+    gb = _max_gb(gb, csr, C)
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_max_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs,
+                                    *_graph_args(gb, csr, C, H * W, flags), _ptr(dx),
+                                    (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb),
+                                    _stream(x.device))
+    _lib.check(code, "mrp_film_max_bwd")
+    PATH_COUNTS["max_bwd_" + _DTYPE_KEYS[dtype]] += 1
+    return dx, dgb
+
+
+class FilmMaxFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = ``mrp_film_max_fwd``, backward = ``mrp_film_max_bwd``.  ``flags`` may be
+    ``_lib.GB_LOGITS`` (gb = pre-sigmoid logits; the gradient is then d logits)."""
+
+    @staticmethod
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int):
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+        film_max_forward_into(x, gb, csr, flags, out)
+        ctx.save_for_backward(x, gb)
+        ctx.csr, ctx.flags = csr, flags
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gb = ctx.saved_tensors
+        dx, dgb = film_max_backward(grad_out, x, gb, ctx.csr, ctx.flags, ctx.needs_input_grad[0],
+                                    ctx.needs_input_grad[1])
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        return dx, dgb, None, None
+
+
+def film_max(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False) -> torch.Tensor:
+    """``max_e(gamma_e * x_src + beta_e)`` per destination node, element-wise over (C, H, W): the reducer
+    ``torch.max(mailbox, 1)`` in place of the reference's mean, with torch's autograd of it (first maximal
+    message on a tie, first NaN wins).
+
+    x: (N, C, H, W) fp32, bf16 or fp16 on a ROCm device (16-bit features are widened exactly, the messages
+    are fp32, the output is rounded once); gb: (E, 2C) or (E, C, 2) interleaved gamma/beta, or their
+    pre-sigmoid logits with ``logits=True``; csr: ``RobotGraph.csr(device)``, every in-degree
+    <= ``_lib.FILM_MAX_DEGREE`` (``ValueError`` otherwise)."""
+    _check_max_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _check_x(x)
+    return FilmMaxFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0)
+
+
+class FilmMaxCatFunction(torch.autograd.Function):
+    """``torch.cat((x, film_max(x, gb)), 1)``: the kernel writes the aggregate into the second half of the
+    (N, 2C, H, W) buffer through its node stride, x is copied into the first half by torch; backward hands
+    the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
+
+    @staticmethod
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int):
+        n, C, H, W = x.shape
+        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        film_max_forward_into(x, gb, csr, flags, buf[:, C:])
+        buf[:, :C].copy_(x)
+        ctx.save_for_backward(x, gb)
+        ctx.csr, ctx.flags = csr, flags
+        return buf
+
+    @staticmethod
+    def backward(ctx, grad_buf):
+        x, gb = ctx.saved_tensors
+        C = x.shape[1]
+        need_dx = ctx.needs_input_grad[0]
+        dx, dgb = film_max_backward(grad_buf[:, C:], x, gb, ctx.csr, ctx.flags, need_dx, ctx.needs_input_grad[1],
+                                    grad_x_base=grad_buf[:, :C] if need_dx else None)
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        return dx, dgb, None, None
+
+
+def film_max_cat(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False) -> torch.Tensor:
+    """``torch.cat((x, film_max(x, gb, csr, logits)), dim=1)`` without a concatenation pass for the aggregate."""
+    _check_max_degree(csr)
+    _check_x(x)
+    return FilmMaxCatFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0)
+
+
+def film_max_residual(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False) -> torch.Tensor:
+    """``x + film_max(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
+    return x + film_max(x, gb, csr, logits)
+
+
+def film_max_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Tensor, alpha: float,
+                 logits: bool = False) -> torch.Tensor:
+    """``(1 - alpha) * film_max(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
+    return (1.0 - float(alpha)) * film_max(x, gb, csr, logits) + float(alpha) * x0

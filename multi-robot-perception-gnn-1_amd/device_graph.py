@@ -79,7 +79,7 @@ def frame_batch(poses: torch.Tensor, knn: Optional[int] = None, max_range: Optio
         kind = _lib.graph_regular(k) if k <= _lib.MAX_REGULAR_K else _lib.GRAPH_CSR
         # edges are destination-major: edge e goes to node e // k; src (CSR order) is in edge order
         edge_fn = lambda: (src.cpu().numpy().astype(np.int64), np.arange(ne, dtype=np.int64) // k)  # noqa: E731
-    csr = GraphCSR(indptr, src, eid, goff, B, n, nt, ne, kind)
+    csr = GraphCSR(indptr, src, eid, goff, B, n, nt, ne, kind, False, max(n - 1, 0))
     g = RobotGraph._from_device(edge_fn, nt, ne, [n] * B, [ne // B if B else 0] * B, csr=csr, device=dev,
                                 complete=(k == 0 and n >= 1) if B else False, kdeg=(k if k else (n - 1 if n > 1 else 0)))
     # the same arrays are a valid CSR description under the other graph kinds too
@@ -118,7 +118,7 @@ def _frame_batch_range(poses: torch.Tensor, B: int, n: int, k: int, max_range, a
                                                    src.data_ptr(), eid.data_ptr(), goff.data_ptr(), ws.data_ptr(),
                                                    nbytes, s.cuda_stream),
                    "mrp_frame_graph_build_range")
-    csr = GraphCSR(indptr, src, eid, goff, B, n, nt, ne, _lib.GRAPH_SIMPLE, True)
+    csr = GraphCSR(indptr, src, eid, goff, B, n, nt, ne, _lib.GRAPH_SIMPLE, True, max(n - 1, 0))
 
     def edge_active():  # one device-to-host copy, only if the host asks
         mask = np.zeros(ne, dtype=bool)

@@ -45,6 +45,8 @@ class GraphCSR(NamedTuple):
     # slots), src / eid have that capacity and list only the existing edges (indptr[-1] of them)
     graph_kind: int
     sparse_eid: bool = False  # the edge ids may leave gamma/beta rows unnamed (a masked graph's arrays)
+    # host-known upper bound of every node's in-degree (-1: unknown); film_max checks it against its limit
+    max_in_degree: int = -1
 
 
 class _FeatureDict(dict):
@@ -279,7 +281,7 @@ class RobotGraph:
         indptr, src, eid, goff, max_nodes = self.host_csr()
         to = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
         csr = GraphCSR(to(indptr), to(src), to(eid), to(goff), len(self._bnn), max_nodes,
-                       self._num_nodes, self.num_edges(), kind)
+                       self._num_nodes, self.num_edges(), kind, False, _max_in_degree(indptr))
         self._csr_cache[key] = csr
         return csr
 
@@ -297,13 +299,18 @@ class RobotGraph:
             pad = lambda a: np.concatenate([a, np.zeros(E - a.shape[0], np.int32)])  # noqa: E731
             to = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
             csr = GraphCSR(to(indptr), to(pad(src)), to(pad(eid)), to(goff), len(self._bnn), max_nodes,
-                           self._num_nodes, E, kind, True)
+                           self._num_nodes, E, kind, True, _max_in_degree(indptr))
         self._csr_cache[(str(device), kind)] = csr
         return csr
 
     def __repr__(self) -> str:
         return (f"RobotGraph(num_nodes={self._num_nodes}, num_edges={self.num_edges()}, "
                 f"batch_size={self.batch_size}, ndata={list(self.ndata)}, edata={list(self.edata)})")
+
+
+def _max_in_degree(indptr: np.ndarray) -> int:
+    """Largest in-degree of a host CSR (0 for a graph without nodes)."""
+    return int(np.diff(indptr).max()) if indptr.shape[0] > 1 else 0
 
 
 def build_csr(src: np.ndarray, dst: np.ndarray, num_nodes: int, batch_num_nodes: Sequence[int]):

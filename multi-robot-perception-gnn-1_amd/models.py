@@ -24,7 +24,8 @@ Semantics switch ``opt.gcn_return``:
   because ``node_udf`` writes ``'images'``; the aggregate is then dead work and is skipped.
 
 ``opt.gcn_mode``: ``'film_mean'`` (default, ``models.py:223``), ``'copy_mean'`` (the commented-out
-``fn.copy_u`` variant, ``models.py:225``), ``'film_sum'``.
+``fn.copy_u`` variant, ``models.py:225``), ``'film_sum'``, ``'film_max'`` (``node_udf`` =
+``torch.max(mailbox, 1)``: :func:`aggregate.film_max`, every in-degree <= 16).
 """
 from __future__ import annotations
 
@@ -33,7 +34,8 @@ import warnings
 import torch
 import torch.nn as nn
 
-from .aggregate import film_mean, film_mean_cat, film_mean_mix, film_mean_residual
+from .aggregate import (film_max, film_max_cat, film_max_mix, film_max_residual, film_mean, film_mean_cat,
+                        film_mean_mix, film_mean_residual)
 from .compress import compress_1x1, compress_path, film_compress, film_compress_supported
 from .encoder import edge_logits
 
@@ -146,6 +148,8 @@ class GCN(_PackedImages, nn.Module):
             return film_mean(x, None, g.csr(x.device), mode)
         # logits in, sigmoid applied inside the aggregation kernel
         z = self.edge_encoder.logits(g.edata["pose"])
+        if mode == "film_max":  # the max reducer: an operator of its own (aggregate.film_max)
+            return film_max(x, z, g.csr(x.device), logits=True)
         return film_mean(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_cat(self, g, feats: torch.Tensor = None) -> torch.Tensor:
@@ -158,6 +162,8 @@ class GCN(_PackedImages, nn.Module):
         if mode == "copy_mean":
             return film_mean_cat(x, None, g.csr(x.device), mode)
         z = self.edge_encoder.logits(g.edata["pose"])
+        if mode == "film_max":
+            return film_max_cat(x, z, g.csr(x.device), logits=True)
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
 
@@ -185,6 +191,8 @@ class GCN(_PackedImages, nn.Module):
             if mode == "copy_mean":
                 return film_compress(conv, x, None, g.csr(x.device), _lib_modes()[mode])
             z = self.edge_encoder.logits(g.edata["pose"])
+            if mode == "film_max":
+                return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="max")
             return film_compress(conv, x, z, g.csr(x.device), _lib_modes()[mode] | _lib_logits())
         return compress_1x1(conv, self.forward_cat(g, x))
 
@@ -198,6 +206,8 @@ class GCN(_PackedImages, nn.Module):
         if mode == "copy_mean":
             return film_mean_residual(x, None, g.csr(x.device), mode)
         z = self.edge_encoder.logits(g.edata["pose"])
+        if mode == "film_max":
+            return film_max_residual(x, z, g.csr(x.device), logits=True)
         return film_mean_residual(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_mix(self, g, feats: torch.Tensor, x0: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -210,6 +220,8 @@ class GCN(_PackedImages, nn.Module):
         if mode == "copy_mean":
             return film_mean_mix(x, None, g.csr(x.device), x0, alpha, mode)
         z = self.edge_encoder.logits(g.edata["pose"])
+        if mode == "film_max":
+            return film_max_mix(x, z, g.csr(x.device), x0, alpha, logits=True)
         return film_mean_mix(x, z, g.csr(x.device), x0, alpha, mode, logits=True)
 
 

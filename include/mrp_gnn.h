@@ -465,6 +465,106 @@ int mrp_film_max_bwd(int32_t dtype,
                      void* stream);
 
 /*
+ * The attention-pooled FiLM aggregation (ABI 22, extended): per-location attention fusion.  At every pixel
+ * the receiver's feature vector is the query, each in-neighbour's FiLM message is key and value, and a
+ * softmax over the row's entries weights them.  An operator of its own with its own kernels (pixel-tile-major:
+ * a workgroup owns a graph and 64 pixels for all channels); the mean and max entry points are unchanged.
+ *
+ * For destination v with CSR row [indptr[v], indptr[v+1]), entries j = 0 .. d-1 in row order (edge-id
+ * order, as mrp_film_max_*), e_j the entry's edge id and u_j its source:
+ *
+ *   m_j[c,p]   = fl(fl(gamma_{e_j}[c] * x[u_j,c,p]) + beta_{e_j}[c])          as film_max: no FMA contraction
+ *   s_j[p]     = scale * sum_c x[v,c,p] * m_j[c,p]                           channels ascending, one chain
+ *   a_j[p]     = exp(s_j[p] - max_k s_k[p]) / sum_k exp(s_k[p] - max_k)      softmax over the row's entries
+ *   out[v,c,p] = sum_j a_j[p] * m_j[c,p]                                     slot order; zeros when d = 0
+ *   attn[e_j,p] = a_j[p]                                                     (E, P) fp32, an output
+ *
+ * and the full autograd of it, the paths through the scores included.  With g = grad_out[v]:
+ *
+ *   da_j[p]   = sum_c g[c,p] * m_j[c,p]
+ *   ds_j[p]   = a_j[p] * (da_j[p] - sum_k a_k[p] * da_k[p])
+ *   dm_j[c,p] = a_j[p] * g[c,p] + scale * ds_j[p] * x[v,c,p]                 value path + key path
+ *   grad_x[v,c,p]   += scale * sum_j ds_j[p] * m_j[c,p]                      query path
+ *   grad_x[u_j,c,p] += gamma_{e_j}[c] * dm_j[c,p]                            (+ grad_x_base)
+ *   grad_gb[e_j,c,0] = sum_p x[u_j,c,p] * dm_j[c,p]
+ *   grad_gb[e_j,c,1] = sum_p dm_j[c,p]
+ *
+ * The backward reads attn as the forward wrote it and recomputes the messages, not the softmax.  With
+ * MRP_AGG_GB_LOGITS gamma/beta = sigmoid(z) formed in the kernel and grad_gb is d z, as for the mean and max.
+ * The caller chooses scale; 1/sqrt(C) is the usual one, 0 gives uniform weights 1/d.  The exponential is
+ * v_exp_f32 on the max-subtracted score (about 1 ulp), the division is IEEE.
+ *
+ * Every CSR entry is its own message: parallel edges are separate candidates and self-loops are allowed (a
+ * self-loop is how a node attends to itself), under every graph kind (MRP_GRAPH_SIMPLE's promise is not
+ * needed).  Rows of attn and of grad_gb that no CSR entry names are written as zeros.  A node of in-degree 0
+ * gets out = 0 and contributes nothing.
+ *
+ * Precondition, not checked on the device: every in-degree is <= MRP_FILM_ATTN_DEGREE;
+ * MRP_GRAPH_REGULAR(k) with k above it is declined.
+ *
+ * 16-bit features: widened exactly on load; messages, scores, weights and every sum are fp32; one
+ * round-to-nearest-even at each store; gamma, beta, attn and grad_gb stay fp32.  The order of every sum is a
+ * function of C, P and the graph only, never of dtype, strides or alignment (every access is one element), so
+ * mrp_film_attn_fwd(T, x) == T(mrp_film_attn_fwd(float(x))) bit for bit, attn is equal bit for bit, and
+ * likewise grad_x (on grad_out, x and grad_x_base widened) and grad_gb.
+ *
+ * Determinism: no atomics, one writer per output element, every sum in a fixed order (scores: channels
+ * ascending; out: slots ascending; grad_x: per wave of the workgroup the destinations v = w, w+4, ... in
+ * slot order, then the four waves in order, then the base; grad_gb: a fixed 64-lane butterfly per pixel tile,
+ * then the tiles in order).
+ *
+ * Non-finite values: a pixel's weights mix all channels of that pixel, so an input NaN or infinity at
+ * (node, channel, pixel) may reach every channel of `out` and every weight at that pixel of the destinations
+ * that receive the node (and of the node itself), and nothing at any other pixel or in any other graph.  In
+ * the backward, grad_x is likewise confined to that pixel of that graph; grad_gb sums over pixels, so the
+ * graph's grad_gb rows may all be affected.
+ *
+ * flags: 0 or MRP_AGG_GB_LOGITS.  grad_x or grad_gb may each be NULL to skip that output; with both NULL the
+ * backward returns success without a launch.  Validation precedes any launch and matches mrp_film_max_*; in
+ * addition hipErrorInvalidValue is returned for a non-finite scale, a NULL attn where there are edges, and a
+ * workspace smaller than needed.  Empty work returns success (a forward without nodes or channels, C == 0,
+ * writes a non-NULL attn as zeros: there is nothing to score).  No allocation, no host synchronisation,
+ * capturable (hipMemsetAsync of attn / grad_gb precedes the kernels of non-COMPLETE graphs).
+ * out_node_stride / g_node_stride let the aggregate and its gradient be the second half of a concatenation
+ * buffer.
+ *
+ * mrp_film_attn_workspace(direction, ...) is the byte count `workspace` must hold (direction 0: forward,
+ * always 0; else backward: the per-tile grad_gb partials where a plane spans several 64-pixel tiles, else 0).
+ * It makes no GPU call.  The backward needs it only where grad_gb is wanted.
+ */
+#define MRP_FILM_ATTN_DEGREE 16
+
+int mrp_film_attn_fwd(int32_t dtype,
+                      const void* x, int64_t x_node_stride,
+                      const float* gb,
+                      const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                      const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                      int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                      int32_t C, int32_t P, int32_t flags,
+                      void* out, int64_t out_node_stride,
+                      float scale, float* attn,
+                      void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
+int mrp_film_attn_bwd(int32_t dtype,
+                      const void* grad_out, int64_t g_node_stride,
+                      const void* x, int64_t x_node_stride,
+                      const float* gb,
+                      const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                      const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                      int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                      int32_t C, int32_t P, int32_t flags,
+                      void* grad_x, int64_t gx_node_stride,
+                      const void* grad_x_base, int64_t base_node_stride,
+                      float* grad_gb,
+                      float scale, const float* attn,
+                      void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
+int64_t mrp_film_attn_workspace(int32_t direction, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

@@ -12,6 +12,8 @@ from .aggregate import (EpilogueSpec, FilmMeanFunction, film_mean, film_mean_cat
                         pixel_strides, set_channels_last)
 from .aggregate import (FilmMaxFunction, film_max, film_max_backward, film_max_cat,  # noqa: F401
                         film_max_forward_into)
+from .aggregate import (FilmAttnCatFunction, FilmAttnFunction, film_attn, film_attn_backward,  # noqa: F401
+                        film_attn_cat, film_attn_forward_into, film_attn_mix, film_attn_residual)
 from . import compat, compress, encoder  # noqa: F401
 from .compress import compress_precision, compress_precision_scope, set_compress_precision  # noqa: F401
 from .compress import channels_last_compress_fp32, set_channels_last_compress_fp32  # noqa: F401

@@ -34,6 +34,9 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_bwd_cl_workspace",
     "mrp_film_max_fwd",
     "mrp_film_max_bwd",
+    "mrp_film_attn_fwd",
+    "mrp_film_attn_bwd",
+    "mrp_film_attn_workspace",
     "mrp_compress_fwd",
     "mrp_compress_weight_transpose",
     "mrp_compress_bwd_data",
@@ -91,6 +94,7 @@ EXPORTED_SYMBOLS = (
 ABI_VERSION = 22
 MAX_NODES = 16
 FILM_MAX_DEGREE = 16  # MRP_FILM_MAX_DEGREE: largest in-degree of the max-pooled aggregation
+FILM_ATTN_DEGREE = 16  # MRP_FILM_ATTN_DEGREE: largest in-degree of the attention-pooled aggregation
 
 HIP_ERROR_NOT_SUPPORTED = 801  # hipErrorNotSupported: a fused path declines this shape
 
@@ -192,6 +196,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_max_fwd.restype = ctypes.c_int
     lib.mrp_film_max_bwd.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, _P]
     lib.mrp_film_max_bwd.restype = ctypes.c_int
+    # the attention-pooled aggregation: film_max's lists plus scale, attn, workspace, workspace_bytes
+    tail = [ctypes.c_float, _P, _P, _I64, _P]
+    lib.mrp_film_attn_fwd.argtypes = lib.mrp_film_max_fwd.argtypes[:-1] + tail
+    lib.mrp_film_attn_fwd.restype = ctypes.c_int
+    lib.mrp_film_attn_bwd.argtypes = lib.mrp_film_max_bwd.argtypes[:-1] + tail
+    lib.mrp_film_attn_bwd.restype = ctypes.c_int
+    lib.mrp_film_attn_workspace.argtypes = [_I32] * 8
+    lib.mrp_film_attn_workspace.restype = ctypes.c_int64
     lib.mrp_tuning_set.argtypes = [ctypes.c_char_p, _I32]
     lib.mrp_tuning_set.restype = ctypes.c_int
     lib.mrp_compress_fwd.argtypes = [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]

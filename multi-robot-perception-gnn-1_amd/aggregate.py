@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -752,3 +753,240 @@ def film_max_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Ten
                  logits: bool = False) -> torch.Tensor:
     """``(1 - alpha) * film_max(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
     return (1.0 - float(alpha)) * film_max(x, gb, csr, logits) + float(alpha) * x0
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Attention-pooled FiLM aggregation: per-location attention fusion (``mrp_film_attn_fwd`` / ``_bwd``).
+#
+#     m_j   = gamma_e * x[src(e)] + beta_e                       for v's in-edges e in edge-id order
+#     s_j   = scale * sum_c x[v, c] * m_j[c]                     per pixel; scale defaults to 1 / sqrt(C)
+#     a     = softmax_j s_j                                      per pixel, over the row's entries
+#     out_v = sum_j a_j * m_j                                    zeros if deg v = 0
+#
+# and its full autograd (value, key and query paths).  The weights are an output: ``attn`` (E, H*W) fp32 by
+# edge id, rows no CSR entry names zero; the backward reads them back and recomputes only the messages.
+# Every CSR entry is its own message (parallel edges, self-loops); every in-degree must be
+# <= ``_lib.FILM_ATTN_DEGREE``.  channels_last features take the copy-first route, as for the max.
+# ---------------------------------------------------------------------------------------------------------
+def _check_attn_degree(csr: GraphCSR) -> None:
+    bound = getattr(csr, "max_in_degree", -1)
+    if bound < 0:
+        raise ValueError("film_attn needs the graph's in-degree bound: GraphCSR.max_in_degree is unknown (-1); "
+                         f"every in-degree must be <= {_lib.FILM_ATTN_DEGREE}")
+    if bound > _lib.FILM_ATTN_DEGREE:
+        raise ValueError(f"film_attn: a node has in-degree {bound}; the limit is {_lib.FILM_ATTN_DEGREE} "
+                         "(MRP_FILM_ATTN_DEGREE)")
+
+
+def _attn_gb(gb, csr, C):
+    if gb is None:
+        raise ValueError("gamma/beta tensor required for film_attn")
+    gb = gb.reshape(csr.num_edges, C, 2)
+    if not gb.is_contiguous() or gb.dtype != torch.float32:
+        gb = gb.contiguous().float()
+    _require_device(gb)
+    return gb
+
+
+def _check_attn_flags(flags: int) -> int:
+    flags = int(flags)
+    if flags not in (0, _lib.GB_LOGITS):
+        raise ValueError(f"film_attn flags must be 0 or GB_LOGITS ({_lib.GB_LOGITS:#x}), got {flags:#x}")
+    return flags
+
+
+def _attn_scale(scale, C: int) -> float:
+    s = 1.0 / math.sqrt(C) if scale is None and C > 0 else (0.0 if scale is None else float(scale))
+    if not math.isfinite(s):
+        raise ValueError(f"film_attn scale must be finite, got {scale!r}")
+    return s
+
+
+def _attn_workspace(lib, direction: int, csr: GraphCSR, C: int, P: int, device):
+    nbytes = lib.mrp_film_attn_workspace(direction, csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes,
+                                         csr.num_edges, C, P)
+    if nbytes <= 0:
+        return None, 0
+    return torch.empty(((nbytes + 3) // 4,), device=device, dtype=torch.float32), nbytes
+
+
+def film_attn_forward_into(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, flags: int, out: torch.Tensor,
+                           scale: Optional[float] = None, attn: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Run ``mrp_film_attn_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
+    half of a ``torch.cat((h, g_h), 1)`` buffer — and return the weights ``attn`` (E, H*W) fp32 (written
+    into the given tensor, else a new one).  ``flags``: 0 or ``_lib.GB_LOGITS``.  No autograd."""
+    _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _require_device(x, out, attn)
+    flags = _check_attn_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    scale = _attn_scale(scale, C)
+    x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
+    os_ = node_stride(out)
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    gb = _attn_gb(gb, csr, C)
+    if attn is None:
+        attn = torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
+    elif tuple(attn.shape) != (csr.num_edges, H * W) or attn.dtype != torch.float32 or not attn.is_contiguous():
+        raise ValueError(f"attn must be a contiguous {(csr.num_edges, H * W)} float32 tensor")
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        ws, nbytes = _attn_workspace(lib, 0, csr, C, H * W, x.device)
+        code = lib.mrp_film_attn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *_graph_args(gb, csr, C, H * W, flags),
+                                     _ptr(out), os_, scale, _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_attn_fwd")
+    PATH_COUNTS["attn_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+    return attn
+
+
+def film_attn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, attn: torch.Tensor, csr: GraphCSR,
+                       flags: int, need_dx: bool, need_dgb: bool, grad_x_base: Optional[torch.Tensor] = None,
+                       scale: Optional[float] = None):
+    """(grad_x or None, grad_gb (E, C, 2) or None) of :func:`film_attn_forward_into`, ``attn`` being the
+    weights it returned; ``grad_x_base`` (N, C, H, W), if given, is added into grad_x by the kernel.  grad_x is
+    NCHW in x's dtype, grad_gb fp32 with every unnamed row zero."""
+    _check_attn_degree(csr)
+    _require_device(grad_out, x, attn)
+    flags = _check_attn_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    scale = _attn_scale(scale, C)
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    # the kernel reads grad_out, the base and attn with x's extents: a mismatch would be an out-of-bounds read
+    if tuple(grad_out.shape) != (n, C, H, W):
+        raise ValueError(f"grad_out must be {(n, C, H, W)}, got {tuple(grad_out.shape)}")
+    if grad_x_base is not None and tuple(grad_x_base.shape) != (n, C, H, W):
+        raise ValueError(f"grad_x_base must be {(n, C, H, W)}, got {tuple(grad_x_base.shape)}")
+    if tuple(attn.shape) != (csr.num_edges, H * W) or attn.dtype != torch.float32:
+        raise ValueError(f"attn must be {(csr.num_edges, H * W)} float32, got {tuple(attn.shape)} {attn.dtype}")
+    if grad_x_base is not None:
+        _require_device(grad_x_base)
+    attn = attn.contiguous()
+    dtype = x.dtype
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
+    grad_out, gs = _as_node_major(grad_out)
+    x, xs = _as_node_major(x)
+    bs = 0
+    if grad_x_base is not None and need_dx:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
+        grad_x_base, bs = _as_node_major(grad_x_base)
+    else:
+        grad_x_base = None
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
+    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    if not (need_dx or need_dgb):
+        return None, None
+    gb = _attn_gb(gb, csr, C)
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        ws, nbytes = _attn_workspace(lib, 1, csr, C, H * W, x.device) if need_dgb else (None, 0)
+        code = lib.mrp_film_attn_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs,
+                                     *_graph_args(gb, csr, C, H * W, flags), _ptr(dx),
+                                     (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb),
+                                     scale, _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_attn_bwd")
+    PATH_COUNTS["attn_bwd_" + _DTYPE_KEYS[dtype]] += 1
+    return dx, dgb
+
+
+class FilmAttnFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = ``mrp_film_attn_fwd``, backward = ``mrp_film_attn_bwd``.  Returns
+    (out, attn); attn is saved for the backward and is not differentiable.  ``flags`` may be
+    ``_lib.GB_LOGITS`` (gb = pre-sigmoid logits; the gradient is then d logits)."""
+
+    @staticmethod
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale):
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+        attn = film_attn_forward_into(x, gb, csr, flags, out, scale)
+        ctx.save_for_backward(x, gb, attn)
+        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_attn):
+        x, gb, attn = ctx.saved_tensors
+        dx, dgb = film_attn_backward(grad_out, x, gb, attn, ctx.csr, ctx.flags, ctx.needs_input_grad[0],
+                                     ctx.needs_input_grad[1], scale=ctx.scale)
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        return dx, dgb, None, None, None
+
+
+def film_attn(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
+              scale: Optional[float] = None, return_weights: bool = False):
+    """Per-location attention over the FiLM messages of each destination's in-neighbours: at every pixel the
+    receiver's feature vector scores each message ``gamma_e * x_src + beta_e`` (``scale`` times their dot
+    product over the channels, ``1/sqrt(C)`` by default), a softmax over the node's in-edges turns the scores
+    into weights, and the output is the weighted sum of the messages; gradients reach x and gb through the
+    values, the keys and the query.
+
+    x: (N, C, H, W) fp32, bf16 or fp16 on a ROCm device (16-bit features are widened exactly; messages,
+    scores and weights are fp32; the output is rounded once); gb: (E, 2C) or (E, C, 2) interleaved
+    gamma/beta, or their pre-sigmoid logits with ``logits=True``; csr: ``RobotGraph.csr(device)``, every
+    in-degree <= ``_lib.FILM_ATTN_DEGREE`` (``ValueError`` otherwise).  A self-loop lets a node attend to
+    itself.  With ``return_weights=True`` returns ``(out, attn)``, attn (E, H*W) fp32 by edge id — the
+    weights saved for the backward, not differentiable."""
+    _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _check_x(x)
+    out, attn = FilmAttnFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale)
+    return (out, attn) if return_weights else out
+
+
+class FilmAttnCatFunction(torch.autograd.Function):
+    """``torch.cat((x, film_attn(x, gb)), 1)``: the kernel writes the aggregate into the second half of the
+    (N, 2C, H, W) buffer through its node stride, x is copied into the first half by torch; backward hands
+    the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
+
+    @staticmethod
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale):
+        n, C, H, W = x.shape
+        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        attn = film_attn_forward_into(x, gb, csr, flags, buf[:, C:], scale)
+        buf[:, :C].copy_(x)
+        ctx.save_for_backward(x, gb, attn)
+        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.mark_non_differentiable(attn)
+        return buf, attn
+
+    @staticmethod
+    def backward(ctx, grad_buf, _grad_attn):
+        x, gb, attn = ctx.saved_tensors
+        C = x.shape[1]
+        need_dx = ctx.needs_input_grad[0]
+        dx, dgb = film_attn_backward(grad_buf[:, C:], x, gb, attn, ctx.csr, ctx.flags, need_dx,
+                                     ctx.needs_input_grad[1], grad_x_base=grad_buf[:, :C] if need_dx else None,
+                                     scale=ctx.scale)
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        return dx, dgb, None, None, None
+
+
+def film_attn_cat(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
+                  scale: Optional[float] = None, return_weights: bool = False):
+    """``torch.cat((x, film_attn(x, gb, csr, logits, scale)), dim=1)`` without a concatenation pass for the
+    aggregate."""
+    _check_attn_degree(csr)
+    _check_x(x)
+    buf, attn = FilmAttnCatFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale)
+    return (buf, attn) if return_weights else buf
+
+
+def film_attn_residual(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
+                       scale: Optional[float] = None) -> torch.Tensor:
+    """``x + film_attn(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
+    return x + film_attn(x, gb, csr, logits, scale)
+
+
+def film_attn_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Tensor, alpha: float,
+                  logits: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+    """``(1 - alpha) * film_attn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
+    return (1.0 - float(alpha)) * film_attn(x, gb, csr, logits, scale) + float(alpha) * x0

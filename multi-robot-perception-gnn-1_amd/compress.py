@@ -827,33 +827,36 @@ class FilmCompressFunction(torch.autograd.Function):
     saved aggregate.  Saves x, gb and the aggregate — not a 2C-channel buffer."""
 
     @staticmethod
-    def forward(ctx, x, gb, weight, bias, csr, mode: int, reducer: str = "mean"):
-        from .aggregate import film_max_forward_into, film_mean_forward_into
+    def forward(ctx, x, gb, weight, bias, csr, mode: int, reducer: str = "mean", scale=None):
+        from .aggregate import film_attn_forward_into, film_max_forward_into, film_mean_forward_into
         n, C, H, W = x.shape
         hip = _PATH[0] != "library"
-        if reducer == "max":
-            # the max reducer (mode: its flags, 0 or GB_LOGITS) has NCHW kernels only: a channels_last x is
-            # copied first and the layer continues on the NCHW route
+        if reducer in ("max", "attn"):
+            # the max and attention reducers (mode: their flags, 0 or GB_LOGITS) have NCHW kernels only: a
+            # channels_last x is copied first and the layer continues on the NCHW route
             x = x.contiguous()
         # a pixel-major 16-bit x: the pixel-major aggregation into a channels_last aggregate, read in place
         # by the pixel-major compress (no layout copy of x, the aggregate or y)
         cl = hip and _cl_route(x)  # decided once: the backward follows the forward's route
         agg = _empty_cl(x.shape, x.device, x.dtype) if cl else torch.empty(x.shape, device=x.device, dtype=x.dtype)
+        attn = None
         if reducer == "max":
             film_max_forward_into(x, gb, csr, mode, agg)
+        elif reducer == "attn":
+            attn = film_attn_forward_into(x, gb, csr, mode, agg, scale)  # the weights: saved for the backward
         else:
             film_mean_forward_into(x, gb, csr, mode, agg)
         prec = _PRECISION[0]  # read once: both gradients of this node run in the forward's mode
         y = _fwd(weight, bias, x, agg, cl=cl, precision=prec) if hip else _lib_forward(weight, bias, x, agg)
-        ctx.save_for_backward(x, gb, agg, weight, bias)
+        ctx.save_for_backward(x, gb, agg, weight, bias, attn)
         ctx.csr, ctx.mode, ctx.has_bias, ctx.hip, ctx.cl, ctx.precision = csr, mode, bias is not None, hip, cl, prec
-        ctx.reducer = reducer  # the aggregation step and its backward dispatch on it
+        ctx.reducer, ctx.scale = reducer, scale  # the aggregation step and its backward dispatch on the reducer
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        from .aggregate import film_max_backward, film_mean_backward
-        x, gb, agg, weight, bias = ctx.saved_tensors
+        from .aggregate import film_attn_backward, film_max_backward, film_mean_backward
+        x, gb, agg, weight, bias, attn = ctx.saved_tensors
         need_x, need_gb = ctx.needs_input_grad[0], gb is not None and ctx.needs_input_grad[1]
         dx = dgb = dw = db = None
         if need_x or need_gb:
@@ -863,6 +866,9 @@ class FilmCompressFunction(torch.autograd.Function):
             if ctx.reducer == "max":
                 dx, dgb = film_max_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                             grad_x_base=gx if need_x else None)
+            elif ctx.reducer == "attn":
+                dx, dgb = film_attn_backward(ga, x, gb, attn, ctx.csr, ctx.mode, need_x, need_gb,
+                                             grad_x_base=gx if need_x else None, scale=ctx.scale)
             else:
                 dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                              grad_x_base=gx if need_x else None,
@@ -875,7 +881,7 @@ class FilmCompressFunction(torch.autograd.Function):
                 _lib_backward_weight(gy, x, agg, ctx.has_bias)
             if not ctx.needs_input_grad[2]:
                 dw = None
-        return dx, dgb, dw, db, None, None, None
+        return dx, dgb, dw, db, None, None, None, None
 
 
 def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
@@ -888,18 +894,23 @@ def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
     return x.dim() == 4 and x.is_cuda and ok and conv_is_plain_1x1(conv, x.shape[1])
 
 
-def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int, reducer: str = "mean") -> torch.Tensor:
+def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int, reducer: str = "mean",
+                  scale=None) -> torch.Tensor:
     """Autograd form of ``conv(torch.cat((x, film_mean(x, gb)), 1))`` without the concatenation
     (:class:`FilmCompressFunction`); the caller checks :func:`film_compress_supported`.  ``reducer="max"``:
-    the aggregate is ``film_max(x, gb)`` and ``mode`` carries its flags (0 or ``GB_LOGITS``)."""
-    if reducer not in ("mean", "max"):
-        raise ValueError(f'reducer must be "mean" or "max", got {reducer!r}')
-    if reducer == "max":
-        # `mode` then carries film_max's flags, not a MODE_* value of the mean: say so here, not deep in the launch
+    the aggregate is ``film_max(x, gb)`` and ``mode`` carries its flags (0 or ``GB_LOGITS``);
+    ``reducer="attn"``: likewise ``film_attn(x, gb, scale=scale)``."""
+    if reducer not in ("mean", "max", "attn"):
+        raise ValueError(f'reducer must be "mean", "max" or "attn", got {reducer!r}')
+    if reducer in ("max", "attn"):
+        # `mode` then carries the operator's flags, not a MODE_* value of the mean: say so here, not deep in the launch
         if int(mode) not in (0, _lib.GB_LOGITS):
-            raise ValueError(f'reducer="max" takes flags 0 or GB_LOGITS ({_lib.GB_LOGITS:#x}) as mode, got {int(mode):#x}')
+            raise ValueError(f'reducer="{reducer}" takes flags 0 or GB_LOGITS ({_lib.GB_LOGITS:#x}) as mode, '
+                             f'got {int(mode):#x}')
         if gb is None:
-            raise ValueError("gamma/beta tensor required for film_max")
+            raise ValueError(f"gamma/beta tensor required for film_{reducer}")
+    if scale is not None and reducer != "attn":
+        raise ValueError('scale belongs to reducer="attn"')
     if gb is not None:
         gb = gb.reshape(csr.num_edges, x.shape[1], 2)
-    return FilmCompressFunction.apply(x, gb, conv.weight, conv.bias, csr, mode, reducer)
+    return FilmCompressFunction.apply(x, gb, conv.weight, conv.bias, csr, mode, reducer, scale)

@@ -1,0 +1,569 @@
+#pragma once
+// film_attn_kernels.hpp — gfx950 kernels of the attention-pooled FiLM aggregation (mrp_film_attn_fwd / _bwd)
+//
+//   m_j[c,p]   = fl(fl(gamma_j[c] * x[u_j,c,p]) + beta_j[c])    j = 0, 1, ... over v's CSR row (edge-id order)
+//   s_j[p]     = scale * sum_c x[v,c,p] * m_j[c,p]
+//   a_j[p]     = softmax_j s_j[p]
+//   out[v,c,p] = sum_j a_j[p] * m_j[c,p]
+//
+// The weights of a pixel need all C channels, so the decomposition is pixel-tile-major, unlike every other
+// aggregation kernel here: a workgroup owns (graph, tile of kAttnTile = 64 pixels) for all channels and all of
+// the graph's nodes.  Lane l of every wave owns pixel 64 tile + l (one element per access: a wave reads a
+// contiguous 256-byte run of a (node, channel) plane in fp32, and no alignment or stride condition exists, so
+// the geometry — and with it the order of every sum — depends on C, P and the graph only, never on the
+// storage type or the pointers).  Wave w owns the destinations v = w, w + 4, w + 8, w + 12: their <= 16
+// scores each (64 registers) stay in that wave's registers from the channel sweep through the softmax to the
+// second sweep, so no score ever crosses a wave and the channel sum of a score is a single ascending chain.
+//
+// Channels are streamed in chunks: the workgroup stages x[u, c, tile] of all n nodes and the chunk's
+// (gamma, beta) per slot in LDS (sigmoid applied once per slot and channel; the next chunk's loads are in
+// flight in registers while the current one is computed: AttnChunk), then every wave reads the
+// sources of its destinations' slots from LDS at a wave-uniform node index — the dynamic register index that
+// costs film_max its select chains is an LDS address here.  A row's first KS slots (KS = 4, 8 or 16, from the
+// graph kind's in-degree bound) are loaded from LDS in one batch and processed without a branch; slots past
+// the row's end hold zeros and are discarded by selects.  (A wave-uniform branch per slot, the first form of
+// these kernels, left every slot its own LDS round trip: 1.7 x slower in the forward at the headline shape.)
+//
+// Forward: sweep A accumulates s, the softmax runs in registers (v_exp_f32 on the max-subtracted score, an
+// IEEE division by the sum), the weights go to attn (E, P); sweep B forms out.
+// Backward: sweep A accumulates da_j = sum_c g[v] m_j, then ds_j = a_j (da_j - sum_k a_k da_k) with a read
+// from attn; sweep B forms dm_j = a_j g[v] + scale ds_j x[v] per channel.  grad_x of the graph's nodes is
+// accumulated in LDS, one lane-private partial per wave (a lane owns its pixel), and the four partials are
+// summed in wave order; d gamma / d beta of a slot are reduced over the tile's 64 pixels by a fixed butterfly
+// and, where a plane spans several tiles, written per tile to a workspace that film_attn_dgb_reduce sums in
+// tile order.  No atomics anywhere.
+
+#include "film_mean_kernels.hpp"
+
+namespace mrp {
+
+constexpr int kAttnSlots = MRP_FILM_ATTN_DEGREE;  // LDS slot stride per destination
+constexpr int kAttnTile = 64;                     // pixels per workgroup: one per lane of a wave
+constexpr int kAttnWaves = kBlock / 64;
+constexpr int kAttnDpw = (MRP_MAX_NODES + kAttnWaves - 1) / kAttnWaves;  // destinations per wave
+constexpr int kAttnFwdChunk = 8;  // channels staged at a time (forward: 16 n x and 16 n (gamma, beta) floats each)
+// backward: + grad_out and 4 lane-private grad_x partials per (channel, node): 4 channels for <= 8 nodes, else 2
+constexpr int kAttnBwdChunkSmall = 4, kAttnBwdChunk = 2;
+
+struct AttnArgs {
+  AggArgs a;         // the mean kernels' argument block (fwd: out = the aggregate; bwd: out = grad_x)
+  int32_t complete;  // MRP_GRAPH_COMPLETE: slots and edge ids are arithmetic, every graph has a.nmax nodes
+  int32_t ntile;     // pixel tiles per plane (grid = graphs x ntile)
+  int32_t nnodes;    // film_attn_dgb_reduce: nodes of the batch
+  float scale;
+  float* attn;       // (E, P) softmax weights by edge id (fwd: written, bwd: read)
+  float* ws;         // backward, ntile > 1: d gamma / d beta partials [ntile][E][C][2]
+  int64_t E;
+};
+
+// LDS of one workgroup for graphs of up to nmax nodes and chunks of ck channels.
+struct AttnLds {
+  float* X;                    // [ck][nmax][64] the chunk's x, widened
+  float2* W;                   // [ck][nmax * 16] (gamma, beta) per slot
+  float* G;                    // backward: [ck][nmax][64] the chunk's grad_out, widened
+  float* D;                    // backward: [4 waves][ck][nmax][64] grad_x partials
+  unsigned long long* slot_u;  // [nmax] the row's local sources, 4 bits each, slot 0 lowest
+  int* slot_e;                 // [nmax * 16] edge id, -1: no such slot
+  int* rowlen;                 // [nmax]
+  __device__ __forceinline__ AttnLds(void* smem, int nmax, int ck, bool bwd) {
+    X = reinterpret_cast<float*>(smem);
+    W = reinterpret_cast<float2*>(X + ck * nmax * kAttnTile);
+    G = reinterpret_cast<float*>(W + ck * nmax * kAttnSlots);
+    D = G + (bwd ? ck * nmax * kAttnTile : 0);
+    slot_u = reinterpret_cast<unsigned long long*>(D + (bwd ? kAttnWaves * ck * nmax * kAttnTile : 0));
+    slot_e = reinterpret_cast<int*>(slot_u + nmax);
+    rowlen = slot_e + nmax * kAttnSlots;
+  }
+};
+
+// Row lengths, sources and edge ids of the graph's rows (film_max's tables).  Ends with a barrier.
+__device__ __forceinline__ void attn_tables(const AttnArgs& m, const AttnLds& L, int b, int node0, int n) {
+  const AggArgs& a = m.a;
+  for (int v = threadIdx.x; v < n; v += blockDim.x) {
+    int beg = 0, deg = 0;
+    if (m.complete) {
+      deg = n - 1;
+    } else {
+      beg = a.kdeg > 0 ? (node0 + v) * a.kdeg : a.indptr[node0 + v];
+      const int end = a.kdeg > 0 ? beg + a.kdeg : a.indptr[node0 + v + 1];
+      deg = min(max(end - beg, 0), kAttnSlots);  // precondition: in-degree <= 16 (clamped: in-bounds anyway)
+    }
+    const int ebase = b * n * (n - 1);
+    unsigned long long word = 0ull;
+    for (int j = 0; j < kAttnSlots; ++j) {
+      int u = 0, e = -1;
+      if (j < deg) {
+        if (m.complete) {
+          u = j < v ? j : j + 1;  // v's in-edges in edge-id order: ascending source
+          e = ebase + u * (n - 1) + (v < u ? v : v - 1);
+        } else {
+          u = a.src[beg + j] - node0;
+          if ((unsigned)u >= (unsigned)n) u = 0;  // rejected on the host; keeps the LDS index in bounds
+          e = a.eid[beg + j];
+        }
+      }
+      word |= (unsigned long long)u << (4 * j);
+      L.slot_e[v * kAttnSlots + j] = e;
+    }
+    L.slot_u[v] = word;
+    L.rowlen[v] = deg;
+  }
+  __syncthreads();
+}
+
+// A chunk on its way from memory to LDS.  Wave w stages the planes of the nodes u = w, w + 4, w + 8, w + 12
+// (its own destinations, so in the backward their grad_out comes along), thread t the (gamma, beta) of slot t.
+// The loads of the next chunk are issued before the current chunk is computed and land in LDS after it: the
+// memory latency lies under the arithmetic, and nothing waits on a load it has just issued.
+template <int CK, bool BWD, typename T>
+struct AttnChunk {
+  T x[CK * kAttnDpw];  // as stored: widened when put (a conversion here would wait for the load it follows)
+  T g[BWD ? CK * kAttnDpw : 1];
+  T b[BWD ? CK * kAttnDpw : 1];  // grad_x_base of the nodes this wave writes
+  float2 w[CK];
+};
+
+// Issue the loads of chunk [c0, c0 + CK) (zeros past C, past the graph's nodes and past the plane's end).
+// my_e: the edge id of slot threadIdx.x (-1: none).  with_base (wave-uniform): also grad_x_base, which only the
+// backward's second sweep reads.
+template <int CK, bool BWD, typename T>
+__device__ __forceinline__ void attn_fetch(const AttnArgs& m, int node0, int n, int c0, int p, bool pin, int my_e,
+                                           AttnChunk<CK, BWD, T>& r, bool with_base = false) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6;
+  const int ck = min(CK, a.C - c0);  // <= 0 past the last chunk: nothing is loaded
+  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P + p;
+  const T* gp = BWD ? static_cast<const T*>(a.g) + (int64_t)node0 * a.gs + (int64_t)c0 * a.P + p : nullptr;
+  const T* bp = BWD && with_base && a.dxb != nullptr
+                    ? static_cast<const T*>(a.dxb) + (int64_t)node0 * a.dxbs + (int64_t)c0 * a.P + p
+                    : nullptr;
+#pragma unroll
+  for (int cl = 0; cl < CK; ++cl) {
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int u = wave + kAttnWaves * i;
+      T xv = (T)0.f, gv = (T)0.f, bv = (T)0.f;
+      if (cl < ck && u < n && pin) {
+        xv = xb[(int64_t)u * a.xs + (int64_t)cl * a.P];
+        if constexpr (BWD) {
+          gv = gp[(int64_t)u * a.gs + (int64_t)cl * a.P];
+          if (bp != nullptr) bv = bp[(int64_t)u * a.dxbs + (int64_t)cl * a.P];
+        }
+      }
+      r.x[cl * kAttnDpw + i] = xv;
+      if constexpr (BWD) {
+        r.g[cl * kAttnDpw + i] = gv;
+        r.b[cl * kAttnDpw + i] = bv;
+      }
+    }
+    float2 w = make_float2(0.f, 0.f);
+    if (cl < ck && my_e >= 0) w = *reinterpret_cast<const float2*>(a.gb + ((int64_t)my_e * a.C + c0 + cl) * 2);
+    r.w[cl] = w;
+  }
+}
+
+// Put a fetched chunk into LDS, between the barrier that ends the previous chunk's reads and the one that
+// publishes this one.  16-bit elements are widened here and the sigmoid of logits is applied here, once per
+// (slot, channel).
+template <int CK, bool BWD, typename T>
+__device__ __forceinline__ void attn_put(const AttnArgs& m, const AttnLds& L, int n, int my_e,
+                                         const AttnChunk<CK, BWD, T>& r) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+#pragma unroll
+  for (int cl = 0; cl < CK; ++cl) {
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int u = wave + kAttnWaves * i;
+      if (u < n) {
+        L.X[(cl * a.nmax + u) * kAttnTile + lane] = (float)r.x[cl * kAttnDpw + i];
+        if constexpr (BWD) L.G[(cl * a.nmax + u) * kAttnTile + lane] = (float)r.g[cl * kAttnDpw + i];
+      }
+    }
+    if ((int)threadIdx.x < n * kAttnSlots) {
+      float2 w = r.w[cl];
+      if (a.logits && my_e >= 0) w = make_float2(sigmoidf(w.x), sigmoidf(w.y));
+      L.W[cl * a.nmax * kAttnSlots + threadIdx.x] = w;
+    }
+  }
+  __syncthreads();
+}
+
+// The wave-uniform description of destination v's row.
+struct AttnRow {
+  int deg;
+  unsigned ulo, uhi;
+  __device__ __forceinline__ AttnRow(const AttnLds& L, int v) {
+    deg = __builtin_amdgcn_readfirstlane(L.rowlen[v]);
+    const unsigned long long uw = L.slot_u[v];
+    ulo = __builtin_amdgcn_readfirstlane((unsigned)uw);
+    uhi = __builtin_amdgcn_readfirstlane((unsigned)(uw >> 32));
+  }
+  __device__ __forceinline__ int src(int jj) const { return ((jj < 8 ? ulo : uhi) >> (4 * (jj & 7))) & 15u; }
+};
+
+// The chunk-channel's (gamma, beta) and source value of a row's first KS slots, loaded from LDS in one batch
+// with no branch in between (a branch per slot leaves every slot its own LDS round trip).  Slots past the
+// row's end hold (0, 0) and source 0: their products are computed and discarded by the callers' selects.
+template <int KS>
+__device__ __forceinline__ void attn_slots(const float* Xc, const float2* Wc, const AttnRow& r, float2 (&w)[KS],
+                                           float (&xu)[KS]) {
+#pragma unroll
+  for (int jj = 0; jj < KS; ++jj) {
+    w[jj] = Wc[jj];
+    xu[jj] = Xc[r.src(jj) * kAttnTile];
+  }
+}
+
+// acc[i][j] += q_i[c,p] * m_j[c,p] over the chunk's ck channels for this wave's destinations; q is x[v] in the
+// forward and grad_out[v] in the backward.  (Accumulators of slots past a row's end collect garbage, unread.)
+template <bool BWD, int KS>
+__device__ __forceinline__ void attn_scores(const AttnArgs& m, const AttnLds& L, int n, int ck,
+                                            float (&acc)[kAttnDpw][KS]) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) {
+    const int v = wave + kAttnWaves * i;
+    if (v >= n) continue;  // wave-uniform
+    const AttnRow r(L, v);
+    for (int cl = 0; cl < ck; ++cl) {
+      const float* Xc = L.X + cl * a.nmax * kAttnTile + lane;
+      const float2* Wc = L.W + cl * a.nmax * kAttnSlots + v * kAttnSlots;
+      const float q = BWD ? L.G[(cl * a.nmax + v) * kAttnTile + lane] : Xc[v * kAttnTile];
+      float2 w[KS];
+      float xu[KS];
+      attn_slots<KS>(Xc, Wc, r, w, xu);
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
+        acc[i][jj] = __fmaf_rn(q, msg, acc[i][jj]);
+      }
+    }
+  }
+}
+
+// Sum over the wave's 64 lanes, valid in lane 63: within rows of 16 by quad_perm, row_half_mirror and row_mirror,
+// then row 0 into 1 and 2 into 3 (row_bcast15), then rows 0-1 into 2-3 (row_bcast31).  DPP only: no LDS round
+// trip, a fixed order.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ float dpp_rows(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ float wave_sum63(float x) {
+  x += dpp_mov<0xB1>(x);
+  x += dpp_mov<0x4E>(x);
+  x += dpp_mov<0x141>(x);
+  x += dpp_mov<0x140>(x);
+  x += dpp_rows<0x142, 0xA>(x);
+  x += dpp_rows<0x143, 0xC>(x);
+  return x;
+}
+
+// ---------------------------------------------------------------------------
+// Forward.  Workgroup = graph x pixel tile.  KS: compiled slots per destination (4, 8 or 16; the launcher picks
+// KS >= the graph kind's in-degree bound).
+// ---------------------------------------------------------------------------
+template <typename T, int KS>
+__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
+  const AggArgs& a = m.a;
+  extern __shared__ float4 smem_f4[];
+  const AttnLds L(smem_f4, a.nmax, kAttnFwdChunk, false);
+  const int b = blockIdx.x / m.ntile;
+  const int tile = blockIdx.x - b * m.ntile;
+  const int node0 = m.complete ? b * a.nmax : a.goff[b];
+  const int n = m.complete ? a.nmax : min(a.goff[b + 1] - node0, a.nmax);
+  if (n <= 0) return;  // whole workgroup: empty graph
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = tile * kAttnTile + lane;
+  const bool pin = p < a.P;
+  attn_tables(m, L, b, node0, n);
+  constexpr int CK = kAttnFwdChunk;
+  const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
+  AttnChunk<CK, false, T> next;
+  attn_fetch<CK, false, T>(m, node0, n, 0, p, pin, my_e, next);
+
+  float s[kAttnDpw][KS];
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i)
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) s[i][jj] = 0.f;
+
+  // sweep A: the scores, each an ascending chain over the channels
+  for (int c0 = 0; c0 < a.C; c0 += CK) {
+    attn_put<CK, false, T>(m, L, n, my_e, next);
+    attn_fetch<CK, false, T>(m, node0, n, c0 + CK < a.C ? c0 + CK : 0, p, pin, my_e, next);  // wraps: sweep B's first
+    attn_scores<false, KS>(m, L, n, min(CK, a.C - c0), s);
+  }
+
+  // softmax over the row's entries, in registers; s becomes the weights
+  constexpr float kLog2e = 1.4426950408889634f;
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) {
+    const int v = wave + kAttnWaves * i;
+    if (v >= n) continue;
+    const int deg = __builtin_amdgcn_readfirstlane(L.rowlen[v]);
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) {
+      if (jj >= deg) continue;
+      s[i][jj] = __fmul_rn(m.scale, s[i][jj]);
+      mx = fmaxf(mx, s[i][jj]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) {
+      if (jj >= deg) continue;
+      s[i][jj] = __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(s[i][jj], mx), kLog2e));
+      sum = __fadd_rn(sum, s[i][jj]);
+    }
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) {
+      if (jj >= deg) continue;
+      s[i][jj] = __fdiv_rn(s[i][jj], sum);
+      const int e = L.slot_e[v * kAttnSlots + jj];
+      if (pin) m.attn[(int64_t)e * a.P + p] = s[i][jj];
+    }
+  }
+
+  // sweep B: out = sum_j a_j m_j in slot order
+  for (int c0 = 0; c0 < a.C; c0 += CK) {
+    const int ck = min(CK, a.C - c0);
+    attn_put<CK, false, T>(m, L, n, my_e, next);
+    attn_fetch<CK, false, T>(m, node0, n, c0 + CK, p, pin, my_e, next);
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int v = wave + kAttnWaves * i;
+      if (v >= n) continue;
+      const AttnRow r(L, v);
+      T* ob = static_cast<T*>(a.out) + (int64_t)(node0 + v) * a.os + (int64_t)c0 * a.P + p;
+      for (int cl = 0; cl < ck; ++cl) {
+        const float* Xc = L.X + cl * a.nmax * kAttnTile + lane;
+        const float2* Wc = L.W + cl * a.nmax * kAttnSlots + v * kAttnSlots;
+        float2 w[KS];
+        float xu[KS];
+        attn_slots<KS>(Xc, Wc, r, w, xu);
+        Frag<1> o;
+        o.v[0] = 0.f;  // empty row: zeros
+#pragma unroll
+        for (int jj = 0; jj < KS; ++jj) {
+          const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
+          const float t = jj == 0 ? __fmul_rn(s[i][jj], msg) : __fmaf_rn(s[i][jj], msg, o.v[0]);
+          o.v[0] = jj < r.deg ? t : o.v[0];  // a select, not a branch (wave-uniform)
+        }
+        if (pin) store_frag<1, true>(ob + (int64_t)cl * a.P, o);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Backward.  Workgroup = graph x pixel tile; a.want_dx / a.want_dgb choose the outputs (the arithmetic of
+// either is the same whether or not the other is wanted).  CK: channels per chunk; KS as in the forward.
+// ---------------------------------------------------------------------------
+template <typename T, int CK, int KS>
+__global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
+  const AggArgs& a = m.a;
+  extern __shared__ float4 smem_f4[];
+  const AttnLds L(smem_f4, a.nmax, CK, true);
+  const int b = blockIdx.x / m.ntile;
+  const int tile = blockIdx.x - b * m.ntile;
+  const int node0 = m.complete ? b * a.nmax : a.goff[b];
+  const int n = m.complete ? a.nmax : min(a.goff[b + 1] - node0, a.nmax);
+  if (n <= 0) return;  // whole workgroup
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = tile * kAttnTile + lane;
+  const bool pin = p < a.P;
+  attn_tables(m, L, b, node0, n);
+  const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
+  AttnChunk<CK, true, T> next;
+  attn_fetch<CK, true, T>(m, node0, n, 0, p, pin, my_e, next);
+
+  float ds[kAttnDpw][KS], at[kAttnDpw][KS];
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i)
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) ds[i][jj] = at[i][jj] = 0.f;
+
+  // sweep A: da_j = sum_c g[v] m_j
+  for (int c0 = 0; c0 < a.C; c0 += CK) {
+    attn_put<CK, true, T>(m, L, n, my_e, next);
+    const bool last = c0 + CK >= a.C;  // then the fetch wraps to sweep B's first chunk, base included
+    attn_fetch<CK, true, T>(m, node0, n, last ? 0 : c0 + CK, p, pin, my_e, next, last);
+    attn_scores<true, KS>(m, L, n, min(CK, a.C - c0), ds);
+  }
+  // ds_j = a_j (da_j - sum_k a_k da_k), kept multiplied by scale (both of its uses are); zeros past the row's end
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) {
+    const int v = wave + kAttnWaves * i;
+    const int deg = v < n ? __builtin_amdgcn_readfirstlane(L.rowlen[v]) : 0;
+    float dot = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj) {
+      if (jj >= deg) continue;
+      const int e = L.slot_e[v * kAttnSlots + jj];
+      at[i][jj] = pin ? m.attn[(int64_t)e * a.P + p] : 0.f;
+      dot = __fmaf_rn(at[i][jj], ds[i][jj], dot);
+    }
+#pragma unroll
+    for (int jj = 0; jj < KS; ++jj)
+      ds[i][jj] = jj < deg ? __fmul_rn(m.scale, __fmul_rn(at[i][jj], __fsub_rn(ds[i][jj], dot))) : 0.f;
+  }
+
+  // sweep B
+  const bool want_dx = a.want_dx != 0, want_dgb = a.want_dgb != 0;
+  for (int c0 = 0; c0 < a.C; c0 += CK) {
+    const int ck = min(CK, a.C - c0);
+    attn_put<CK, true, T>(m, L, n, my_e, next);
+    T base[CK * kAttnDpw];  // this chunk's grad_x_base, kept while the next chunk is fetched
+#pragma unroll
+    for (int t = 0; t < CK * kAttnDpw; ++t) base[t] = next.b[t];
+    attn_fetch<CK, true, T>(m, node0, n, c0 + CK, p, pin, my_e, next, true);
+    float* Dw = L.D + wave * CK * a.nmax * kAttnTile + lane;  // this lane's partials: [cl][u]
+    if (want_dx) {
+      // lane-private: written after the barriers that ended the previous chunk's sum, read by this lane only
+      // until the barrier below
+      for (int t = 0; t < ck * a.nmax; ++t) Dw[t * kAttnTile] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int v = wave + kAttnWaves * i;
+      if (v >= n) continue;
+      const AttnRow r(L, v);
+      for (int cl = 0; cl < ck; ++cl) {
+        const int c = c0 + cl;
+        const float* Xc = L.X + cl * a.nmax * kAttnTile + lane;
+        const float2* Wc = L.W + cl * a.nmax * kAttnSlots + v * kAttnSlots;
+        float* Dc = Dw + cl * a.nmax * kAttnTile;
+        const float g = L.G[(cl * a.nmax + v) * kAttnTile + lane];
+        const float xv = Xc[v * kAttnTile];
+        float2 w[KS];
+        float xu[KS];
+        attn_slots<KS>(Xc, Wc, r, w, xu);
+        float qacc = 0.f;  // the query path: scale sum_j ds_j m_j
+#pragma unroll
+        for (int jj = 0; jj < KS; ++jj) {
+          const bool used = jj < r.deg;  // wave-uniform; selects, not branches
+          const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
+          float dm = __fmaf_rn(ds[i][jj], xv, __fmul_rn(at[i][jj], g));  // key path + value path
+          dm = used ? dm : 0.f;
+          qacc = used ? __fmaf_rn(ds[i][jj], msg, qacc) : qacc;
+          if (want_dx) {
+            // (gamma, dm) = (0, 0) past the row's end: the partial of node 0 is rewritten unchanged
+            float* Du = Dc + r.src(jj) * kAttnTile;
+            *Du = __fmaf_rn(w[jj].x, dm, *Du);
+          }
+          if (want_dgb) {
+            float2 rsum = make_float2(wave_sum63(used ? __fmul_rn(xu[jj], dm) : 0.f), wave_sum63(dm));
+            if (lane == 63 && used) {
+              const int e = L.slot_e[v * kAttnSlots + jj];
+              const int64_t off = ((int64_t)e * a.C + c) * 2;
+              if (m.ntile > 1) {
+                *reinterpret_cast<float2*>(m.ws + (int64_t)tile * m.E * a.C * 2 + off) = rsum;
+              } else {
+                if (a.logits) rsum = sigmoid_backward(rsum, *reinterpret_cast<const float2*>(a.gb + off));
+                *reinterpret_cast<float2*>(a.dgb + off) = rsum;
+              }
+            }
+          }
+        }
+        if (want_dx) Dc[v * kAttnTile] = __fadd_rn(Dc[v * kAttnTile], qacc);
+      }
+    }
+    if (want_dx) {
+      __syncthreads();
+      // grad_x of the chunk: the four waves' partials in wave order, then the base.  Wave w writes the nodes
+      // it staged (u = w, w + 4, ...).
+      T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P + p;
+#pragma unroll
+      for (int cl = 0; cl < CK; ++cl) {
+#pragma unroll
+        for (int i = 0; i < kAttnDpw; ++i) {
+          const int u = wave + kAttnWaves * i;
+          if (cl >= ck || u >= n) continue;
+          const float* Dp = L.D + (cl * a.nmax + u) * kAttnTile + lane;
+          Frag<1> o;
+          o.v[0] = Dp[0];
+#pragma unroll
+          for (int w = 1; w < kAttnWaves; ++w) o.v[0] = __fadd_rn(o.v[0], Dp[w * CK * a.nmax * kAttnTile]);
+          if (a.dxb != nullptr) o.v[0] = __fadd_rn(o.v[0], (float)base[cl * kAttnDpw + i]);
+          if (pin) store_frag<1, true>(ob + (int64_t)u * a.os + (int64_t)cl * a.P, o);
+        }
+      }
+    }
+  }
+}
+
+}  // namespace mrp
+
+namespace mrp_host {
+
+using mrp::AttnArgs;
+
+inline int attn_tiles(int32_t P) { return (P + mrp::kAttnTile - 1) / mrp::kAttnTile; }
+
+inline int attn_bwd_chunk(int max_nodes) { return max_nodes <= 8 ? mrp::kAttnBwdChunkSmall : mrp::kAttnBwdChunk; }
+
+inline size_t lds_attn(int nmax, int ck, bool bwd) {
+  return (size_t)ck * nmax * mrp::kAttnTile * 4 * (bwd ? 2 + mrp::kAttnWaves : 1) +
+         (size_t)ck * nmax * mrp::kAttnSlots * 8 + (size_t)nmax * 8 + (size_t)nmax * mrp::kAttnSlots * 4 +
+         (size_t)nmax * 4;
+}
+
+// bytes of the backward's grad_gb workspace
+inline int64_t attn_workspace_bytes(int32_t num_edges, int32_t C, int32_t P) {
+  const int nt = attn_tiles(P);
+  return nt > 1 ? (int64_t)nt * num_edges * C * 2 * (int64_t)sizeof(float) : 0;
+}
+
+// The argument checks the two entry points share (film_max's, plus the scale).
+inline bool attn_common_ok(int32_t dtype, int32_t flags, const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                           const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                           int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, float scale) {
+  if (dtype != MRP_DTYPE_F32 && dtype != MRP_DTYPE_BF16 && dtype != MRP_DTYPE_F16) return false;
+  if (flags != 0 && flags != MRP_AGG_GB_LOGITS) return false;
+  if (!common_args_ok(indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P,
+                      MRP_AGG_FILM_MEAN))
+    return false;
+  if (MRP_GRAPH_IS_REGULAR(graph_kind) && MRP_GRAPH_REGULAR_K(graph_kind) > MRP_FILM_ATTN_DEGREE) return false;
+  return scale == scale && scale - scale == 0.f;  // finite
+}
+
+// compiled slots per destination for the in-degree bound a graph kind gives (COMPLETE: n - 1, REGULAR(k): k,
+// else the operator's limit)
+inline int attn_slots_for(int32_t graph_kind, int32_t max_nodes) {
+  const int maxdeg = graph_kind == MRP_GRAPH_COMPLETE
+                         ? max_nodes - 1
+                         : (MRP_GRAPH_IS_REGULAR(graph_kind) ? MRP_GRAPH_REGULAR_K(graph_kind) : MRP_FILM_ATTN_DEGREE);
+  return maxdeg <= 4 ? 4 : (maxdeg <= 8 ? 8 : 16);
+}
+
+hipError_t launch_attn_bwd_f32(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+hipError_t launch_attn_bwd_bf16(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+hipError_t launch_attn_bwd_f16(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+
+template <typename T>
+hipError_t launch_attn_bwd(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st) {
+  const dim3 g((unsigned)grid), block(mrp::kBlock);
+#define MRP_ATTN_BWD(CK, KS) hipLaunchKernelGGL((mrp::film_attn_bwd<T, CK, KS>), g, block, lds, st, m)
+  if (ck == mrp::kAttnBwdChunkSmall) {  // <= 8 nodes: in-degree <= 8 for every kind but CSR / SIMPLE rows
+    if (ks == 4)
+      MRP_ATTN_BWD(mrp::kAttnBwdChunkSmall, 4);
+    else if (ks == 8)
+      MRP_ATTN_BWD(mrp::kAttnBwdChunkSmall, 8);
+    else
+      MRP_ATTN_BWD(mrp::kAttnBwdChunkSmall, 16);
+  } else {
+    if (ks == 4)
+      MRP_ATTN_BWD(mrp::kAttnBwdChunk, 4);
+    else if (ks == 8)
+      MRP_ATTN_BWD(mrp::kAttnBwdChunk, 8);
+    else
+      MRP_ATTN_BWD(mrp::kAttnBwdChunk, 16);
+  }
+#undef MRP_ATTN_BWD
+  return hipGetLastError();
+}
+
+}  // namespace mrp_host

@@ -25,7 +25,9 @@ Semantics switch ``opt.gcn_return``:
 
 ``opt.gcn_mode``: ``'film_mean'`` (default, ``models.py:223``), ``'copy_mean'`` (the commented-out
 ``fn.copy_u`` variant, ``models.py:225``), ``'film_sum'``, ``'film_max'`` (``node_udf`` =
-``torch.max(mailbox, 1)``: :func:`aggregate.film_max`, every in-degree <= 16).
+``torch.max(mailbox, 1)``: :func:`aggregate.film_max`, every in-degree <= 16), ``'film_attn'`` (per-location
+attention over the messages: :func:`aggregate.film_attn`, every in-degree <= 16; ``opt.gcn_attn_scale``
+sets the score scale, default ``None``: 1/sqrt(C)).
 """
 from __future__ import annotations
 
@@ -34,8 +36,8 @@ import warnings
 import torch
 import torch.nn as nn
 
-from .aggregate import (film_max, film_max_cat, film_max_mix, film_max_residual, film_mean, film_mean_cat,
-                        film_mean_mix, film_mean_residual)
+from .aggregate import (film_attn, film_attn_cat, film_attn_mix, film_attn_residual, film_max, film_max_cat,
+                        film_max_mix, film_max_residual, film_mean, film_mean_cat, film_mean_mix, film_mean_residual)
 from .compress import compress_1x1, compress_path, film_compress, film_compress_supported
 from .encoder import edge_logits
 
@@ -137,6 +139,10 @@ class GCN(_PackedImages, nn.Module):
     def _return_mode(self) -> str:
         return _opt(self.opt, "gcn_return", self.__dict__.get("gcn_return_default", "aggregate"))
 
+    def _attn_scale(self):
+        """``opt.gcn_attn_scale``: the score scale of ``gcn_mode='film_attn'`` (None: 1/sqrt(C))."""
+        return _opt(self.opt, "gcn_attn_scale", None)
+
     def forward(self, g, feats: torch.Tensor = None) -> torch.Tensor:
         """The aggregate of ``feats`` (fp32, bf16 or fp16; returned in that dtype — the encoder's logits
         stay fp32 and the aggregation's arithmetic is fp32 either way)."""
@@ -150,6 +156,8 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":  # the max reducer: an operator of its own (aggregate.film_max)
             return film_max(x, z, g.csr(x.device), logits=True)
+        if mode == "film_attn":  # per-location attention over the messages (aggregate.film_attn)
+            return film_attn(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_cat(self, g, feats: torch.Tensor = None) -> torch.Tensor:
@@ -164,6 +172,8 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_cat(x, z, g.csr(x.device), logits=True)
+        if mode == "film_attn":
+            return film_attn_cat(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
 
@@ -193,6 +203,9 @@ class GCN(_PackedImages, nn.Module):
             z = self.edge_encoder.logits(g.edata["pose"])
             if mode == "film_max":
                 return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="max")
+            if mode == "film_attn":
+                return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="attn",
+                                     scale=self._attn_scale())
             return film_compress(conv, x, z, g.csr(x.device), _lib_modes()[mode] | _lib_logits())
         return compress_1x1(conv, self.forward_cat(g, x))
 
@@ -208,6 +221,8 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_residual(x, z, g.csr(x.device), logits=True)
+        if mode == "film_attn":
+            return film_attn_residual(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean_residual(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_mix(self, g, feats: torch.Tensor, x0: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -222,6 +237,8 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_mix(x, z, g.csr(x.device), x0, alpha, logits=True)
+        if mode == "film_attn":
+            return film_attn_mix(x, z, g.csr(x.device), x0, alpha, logits=True, scale=self._attn_scale())
         return film_mean_mix(x, z, g.csr(x.device), x0, alpha, mode, logits=True)
 
 

@@ -54,7 +54,10 @@
  *    (edge, channel).  Every store to bf16 / fp16 is one round to nearest even of the fp32 result:
  *    overflow gives +-inf, results in T's subnormal range are kept, NaN stays NaN, -0 stays -0; bf16 / fp16
  *    subnormal operands are kept by the matrix cores.  The domain of the split-bf16 kernels is stated at
- *    mrp_compress_fwd_split.
+ *    mrp_compress_fwd_split.  FP8 messages (mrp_film_mean_fwd_q): an E4M3 NaN code (0x7f / 0xff) and an
+ *    E5M2 inf / NaN code decode to fp32 NaN / inf and from there propagate as above — to the destinations
+ *    that consume that source, at that channel and pixel, and to no other element; FP8 subnormal codes are
+ *    decoded exactly (no flush), and the product with the scale is one fp32 rounding.
  */
 #ifndef MRP_GNN_H
 #define MRP_GNN_H
@@ -1101,6 +1104,71 @@ int mrp_film_mean_bwd_plan(int32_t dtype,
                            float* grad_gb,
                            const mrp_agg_epilogue* epilogue,
                            mrp_agg_plan* plan);
+
+/*
+ * FP8 messages: the FiLM-mean forward on feature maps that arrive quantised to 8 bits (what a robot
+ * sends over the radio link), read natively and widened exactly in registers.  Added to ABI 22 without a
+ * new number (nothing existing changed; every other entry point still rejects these codes).
+ *
+ *   xq       (num_nodes, C, P) one OCP FP8 code per element: MRP_QDTYPE_E4M3 = torch.float8_e4m3fn (no
+ *            infinities, NaN = 0x7f / 0xff, largest finite 448), MRP_QDTYPE_E5M2 = torch.float8_e5m2
+ *            (IEEE-like, largest finite 57344).  Never the FNUZ encodings.  x_node_stride counts
+ *            elements = bytes.
+ *   x_scale  (num_nodes, C) contiguous fp32, one scale per (source node, channel); NULL: all 1.
+ *   out      (num_nodes, C, P) of out_dtype (MRP_DTYPE_F32, _BF16 or _F16), node stride in its elements.
+ *   the graph arguments, gb and mode (with MRP_AGG_GB_LOGITS) exactly as mrp_film_mean_fwd_t.
+ *
+ * Every loaded code is decoded exactly (subnormal codes included) and multiplied once by its scale,
+ *     x^[u, c, p] = fl32(x_scale[u, c] * decode(xq[u, c, p])),
+ * the scale is never folded into gamma, and from there on the arithmetic is the fp32 kernel's, operation
+ * for operation, with one round to nearest even at the store: for every graph kind, mode and epilogue
+ *     mrp_film_mean_fwd_q(xq, x_scale, out_dtype T) == T(mrp_film_mean_fwd_ex(x^))        bit for bit.
+ * Epilogue: out[v] = agg_scale * a + x0_scale * x0[v] with x0 in out_dtype (residual: x0 = the layer's
+ * own unquantised features, x0_scale 1; mix: agg_scale 1 - alpha, x0 = h0, x0_scale alpha).  A robot's own
+ * features never cross the link, so the own-feature terms cannot come from xq: self_scale != 0 or a
+ * non-NULL xcopy returns hipErrorInvalidValue.
+ * Special values: the E4M3 NaN codes and the E5M2 inf / NaN codes propagate like any fp32 NaN / inf — to
+ * the destinations that have that source as an in-neighbour, at that channel and pixel, and to no other
+ * element; FP8 subnormal codes are decoded exactly; a non-finite scale acts on its (node, channel) alone.
+ * Slices are 8 elements (graphs of <= 8 nodes, 16-bit outputs), 4, or 1: the widest for which xq (1-byte
+ * elements) and out / x0 (2- or 4-byte elements) are both aligned and P and every node stride are
+ * multiples of it.  fp32 outputs use 4 or 1 (16-byte stores, the fp32 kernel's width).
+ * Span: as the typed entry point — node offsets are 64-bit, so xq and out may each span any number of
+ * GiB (tests/test_gpu_fp8_messages.py places node blocks more than 2^32 bytes apart); the byte offsets
+ * within one workgroup's channel block are 32-bit.  No span is declined.
+ * Return codes, all before any launch: hipErrorInvalidValue for an unknown qdtype or out_dtype, a NULL
+ * pointer with work to do, a node stride < C * P, max_nodes > MRP_MAX_NODES, an unknown graph kind or
+ * mode flags, self_scale != 0 or xcopy != NULL.  Zero sizes succeed without a launch.  No host
+ * synchronisation; stream-capturable.  mrp_film_mean_fwd_q_plan: the same arguments without the stream,
+ * host only (no GPU call), reporting the plan the launcher acts on (as mrp_film_mean_fwd_plan).
+ * Not provided: pixel-major FP8 inputs, FP8 outputs, film_max / film_attn on FP8, a backward that reads FP8.
+ */
+enum mrp_qdtype { MRP_QDTYPE_E4M3 = 0, MRP_QDTYPE_E5M2 = 1 };
+
+int mrp_film_mean_fwd_q(int32_t qdtype,
+                        const void* xq, int64_t x_node_stride,
+                        const float* x_scale,
+                        int32_t out_dtype,
+                        const float* gb,
+                        const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                        const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                        int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                        int32_t C, int32_t P, int32_t mode,
+                        void* out, int64_t out_node_stride,
+                        const mrp_agg_epilogue* epilogue,
+                        void* stream);
+int mrp_film_mean_fwd_q_plan(int32_t qdtype,
+                             const void* xq, int64_t x_node_stride,
+                             const float* x_scale,
+                             int32_t out_dtype,
+                             const float* gb,
+                             const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                             const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                             int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                             int32_t C, int32_t P, int32_t mode,
+                             void* out, int64_t out_node_stride,
+                             const mrp_agg_epilogue* epilogue,
+                             mrp_agg_plan* plan);
 
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
  * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature

@@ -10,6 +10,8 @@ from ._lib import MAX_NODES, MAX_REGULAR_K, MODES, graph_regular, load_library  
 from .aggregate import (EpilogueSpec, FilmMeanFunction, film_mean, film_mean_cat,  # noqa: F401
                         film_mean_cat_forward_into, film_mean_forward_into, film_mean_mix, film_mean_residual,
                         pixel_strides, set_channels_last)
+from .aggregate import (dequantize_features, film_mean_fq, film_mean_q, film_mean_q_forward_into,  # noqa: F401
+                        quantize_features)
 from .aggregate import (FilmMaxFunction, film_max, film_max_backward, film_max_cat,  # noqa: F401
                         film_max_forward_into)
 from .aggregate import (FilmAttnCatFunction, FilmAttnFunction, film_attn, film_attn_backward,  # noqa: F401

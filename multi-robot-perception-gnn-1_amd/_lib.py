@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_bwd_t",
     "mrp_film_mean_fwd_plan",
     "mrp_film_mean_bwd_plan",
+    "mrp_film_mean_fwd_q",
+    "mrp_film_mean_fwd_q_plan",
     "mrp_film_mean_bwd_workspace",
     "mrp_film_mean_fwd_cl",
     "mrp_film_mean_bwd_cl",
@@ -105,6 +107,8 @@ GB_LOGITS = 0x100  # mode flag: gb holds pre-sigmoid logits
 DTYPE_F32 = 0  # enum mrp_dtype: the feature storage type of the typed entry points
 DTYPE_BF16 = 1
 DTYPE_F16 = 2
+QDTYPE_E4M3 = 0  # enum mrp_qdtype: the FP8 format of mrp_film_mean_fwd_q's messages (OCP, never FNUZ)
+QDTYPE_E5M2 = 1
 GRAPH_CSR = 0
 GRAPH_COMPLETE = 1
 GRAPH_SIMPLE = 3  # CSR arrays in which no two entries share a (source, destination) pair
@@ -181,6 +185,11 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_mean_fwd_plan.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_plan.argtypes = [_I32, _P, _I64, _P, _I64, _P] + graph + [_P, _I64, _P, _I64, _P, ep, plan]
     lib.mrp_film_mean_bwd_plan.restype = ctypes.c_int
+    # FP8 messages: qdtype, xq, stride, x_scale, out_dtype, then the typed forward's tail
+    lib.mrp_film_mean_fwd_q.argtypes = [_I32, _P, _I64, _P, _I32, _P] + graph + [_P, _I64, ep, _P]
+    lib.mrp_film_mean_fwd_q.restype = ctypes.c_int
+    lib.mrp_film_mean_fwd_q_plan.argtypes = [_I32, _P, _I64, _P, _I32, _P] + graph + [_P, _I64, ep, plan]
+    lib.mrp_film_mean_fwd_q_plan.restype = ctypes.c_int
     lib.mrp_film_mean_bwd_workspace.argtypes = [_I32, _I32, _I32, _I32, _I32]
     lib.mrp_film_mean_bwd_workspace.restype = ctypes.c_int64
     epc = ctypes.POINTER(EpilogueCl)

@@ -562,6 +562,201 @@ def film_mean_cat(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, mo
 
 
 # ---------------------------------------------------------------------------------------------------------
+# FP8 messages (``mrp_film_mean_fwd_q``): feature maps that crossed the radio link quantised to 8 bits are
+# aggregated as they arrive.  The kernel decodes every code exactly and multiplies it once by its
+# per-(source node, channel) scale, x^ = fl32(s * decode(q)); from there on it is the fp32 kernel, operation
+# for operation, with one rounding at the store:
+#
+#     film_mean_q(xq, s, ..., out_dtype=T) == film_mean(dequantize_features(xq, s), ...).to(T)    bit for bit
+#
+# for every graph kind, mode, ``logits``, epilogue and T.  ``film_mean_q`` is an inference op;
+# ``film_mean_fq`` is the differentiable fake-quant route on the existing fp32 kernels, with the same forward
+# bits.  OCP FP8 only (``torch.float8_e4m3fn`` / ``torch.float8_e5m2``), never the FNUZ encodings.  Not
+# provided: pixel-major FP8 kernels (a channels_last FP8 tensor is made NCHW-contiguous first), FP8 for
+# film_max / film_attn, FP8 outputs (quantising is left to torch: ``quantize_features``), FP8 backward.
+# ---------------------------------------------------------------------------------------------------------
+#: fmt -> (torch dtype, largest finite value, enum mrp_qdtype)
+QUANT_FORMATS = {"e4m3": (torch.float8_e4m3fn, 448.0, _lib.QDTYPE_E4M3),
+                 "e5m2": (torch.float8_e5m2, 57344.0, _lib.QDTYPE_E5M2)}
+_QDTYPES = {dt: (name, code) for name, (dt, _fmax, code) in QUANT_FORMATS.items()}
+
+
+def quantize_features(x: torch.Tensor, fmt: str = "e4m3", per: str = "channel"):
+    """``(xq, scale)``: x (N, C, H, W) as FP8 codes with one fp32 scale per (node, channel) — what a robot
+    would transmit.  torch ops only (CPU or GPU), no autograd.
+
+    ``a = amax |x|`` over (H, W) (``per="channel"``) or over (C, H, W) (``per="node"``) in fp32;
+    ``s = a / FMAX`` where ``a > 0``, else 1 (FMAX = 448 for ``"e4m3"``, 57344 for ``"e5m2"``);
+    ``xq = (x.float() / s).clamp(-FMAX, FMAX).to(float8)``, NCHW-contiguous.  ``scale`` is always a
+    contiguous fp32 (N, C) (``per="node"``: the node's scale repeated).  Non-finite features are outside
+    the contract (an infinite amax gives an infinite scale and NaN codes)."""
+    if fmt not in QUANT_FORMATS:
+        raise ValueError(f"fmt must be one of {tuple(QUANT_FORMATS)}, got {fmt!r}")
+    if per not in ("channel", "node"):
+        raise ValueError(f'per must be "channel" or "node", got {per!r}')
+    if x.dim() != 4:
+        raise ValueError(f"node features must be (N, C, H, W), got {tuple(x.shape)}")
+    qdtype, fmax, _code = QUANT_FORMATS[fmt]
+    n, C = x.shape[:2]
+    with torch.no_grad():
+        xf = x.detach().float()
+        if xf.numel() == 0:
+            return torch.empty(x.shape, device=x.device, dtype=qdtype), torch.ones((n, C), device=x.device)
+        if per == "channel":
+            a = xf.abs().amax(dim=(2, 3))
+        else:
+            a = xf.abs().amax(dim=(1, 2, 3)).unsqueeze(1).expand(n, C)
+        s = torch.where(a > 0, a / fmax, torch.ones_like(a)).contiguous()
+        xq = (xf / s[:, :, None, None]).clamp(-fmax, fmax).to(qdtype).contiguous()
+    return xq, s
+
+
+def _q_scale(scale: Optional[torch.Tensor], n: int, C: int) -> Optional[torch.Tensor]:
+    """scale as (N, C): given as (N,), (N, 1) or (N, C)."""
+    if scale is None:
+        return None
+    if scale.dim() == 1:
+        scale = scale.unsqueeze(1)
+    if scale.dim() != 2 or scale.shape[0] != n or scale.shape[1] not in (1, C):
+        raise ValueError(f"scale must be ({n},), ({n}, 1) or ({n}, {C}), got {tuple(scale.shape)}")
+    return scale.expand(n, C)
+
+
+def dequantize_features(xq: torch.Tensor, scale: Optional[torch.Tensor]) -> torch.Tensor:
+    """``xq.float() * scale[:, :, None, None]`` in fp32: exactly the x^ the kernel forms in registers (the
+    decode is exact, the product one fp32 rounding).  ``scale``: (N,), (N, 1), (N, C) or None (all 1)."""
+    if xq.dtype not in _QDTYPES:
+        raise TypeError(f"xq must be float8_e4m3fn or float8_e5m2, got {xq.dtype}")
+    if xq.dim() != 4:
+        raise ValueError(f"quantised features must be (N, C, H, W), got {tuple(xq.shape)}")
+    xf = xq.float()
+    if scale is None:
+        return xf
+    return xf * _q_scale(scale, xq.shape[0], xq.shape[1]).float()[:, :, None, None]
+
+
+def _dense_node_stride(t: torch.Tensor) -> Optional[int]:
+    """``node_stride`` without its dtype check (FP8 codes)."""
+    n, c, h, w = t.shape
+    if n == 0 or c * h * w == 0:
+        return c * h * w
+    s = t.stride()
+    if (w == 1 or s[3] == 1) and (h == 1 or s[2] == w) and (c == 1 or s[1] == h * w) and (n == 1 or s[0] >= c * h * w):
+        return s[0] if n > 1 else c * h * w
+    return None
+
+
+def film_mean_q_forward_into(xq: torch.Tensor, scale: Optional[torch.Tensor], gb: Optional[torch.Tensor],
+                             csr: GraphCSR, out: torch.Tensor, mode="film_mean", logits: bool = False,
+                             x0: Optional[torch.Tensor] = None, agg_scale: float = 1.0,
+                             x0_scale: float = 0.0) -> torch.Tensor:
+    """:func:`film_mean_q` into ``out`` (N, C, H, W) fp32 / bf16 / fp16 — which may be a strided view with a
+    contiguous block per node, such as the second half of a ``torch.cat((h, g_h), 1)`` buffer."""
+    if xq.dtype not in _QDTYPES:
+        raise TypeError(f"xq must be float8_e4m3fn or float8_e5m2 (quantize_features), got {xq.dtype}")
+    if xq.dim() != 4:
+        raise ValueError(f"quantised features must be (N, C, H, W), got {tuple(xq.shape)}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (gb, x0, scale)):
+        raise RuntimeError("mrp_gnn: film_mean_q is an inference op and would drop the gradient of gb / x0; "
+                           "run it under torch.no_grad(), or train through film_mean_fq (same forward bits)")
+    n, C, H, W = xq.shape
+    if n != csr.num_nodes:
+        raise ValueError(f"xq has {n} nodes, graph has {csr.num_nodes}")
+    if out.dim() != 4 or tuple(out.shape) != (n, C, H, W):
+        raise ValueError(f"out must be {(n, C, H, W)}, got {tuple(out.shape)}")
+    if out.dtype not in FEATURE_DTYPES:
+        raise TypeError(f"out must be float32, bfloat16 or float16 (FP8 outputs are not provided), got {out.dtype}")
+    os_ = node_stride(out)
+    if os_ is None:
+        raise ValueError("out must have a contiguous C*H*W block per node (pixel-major FP8 kernels are not provided)")
+    _require_device(xq, out, scale)
+    xs = _dense_node_stride(xq)
+    if xs is None:  # channels_last or otherwise strided codes: made NCHW-contiguous first
+        xq = xq.contiguous()
+        xs = C * H * W
+    sc = _q_scale(scale, n, C)
+    if sc is not None:
+        sc = sc.float().contiguous()
+    m = _mode_flags(mode, logits)
+    gb = _gb_fp32(gb, csr, C, m)
+    ep, keep = None, None
+    if x0 is not None or float(agg_scale) != 1.0:
+        x0p = x0s = 0
+        if x0 is not None:
+            if tuple(x0.shape) != (n, C, H, W):
+                raise ValueError(f"x0 must have the node features' shape {(n, C, H, W)}")
+            _require_device(x0)
+            keep, x0s = _as_node_major(x0.detach().to(out.dtype) if x0.dtype != out.dtype else x0.detach())
+            x0p = keep.data_ptr()
+        ep = _lib.Epilogue(float(agg_scale), 0.0, x0p, x0s, float(x0_scale) if x0 is not None else 0.0, 0, 0)
+    name, code = _QDTYPES[xq.dtype]
+    lib = _lib.load_library()
+    with torch.cuda.device(xq.device):
+        rc = lib.mrp_film_mean_fwd_q(code, _ptr(xq), xs, _ptr(sc), FEATURE_DTYPES[out.dtype],
+                                     *_graph_args(gb, csr, C, H * W, m), _ptr(out), os_,
+                                     ctypes.byref(ep) if ep is not None else None, _stream(xq.device))
+    _lib.check(rc, "mrp_film_mean_fwd_q")
+    PATH_COUNTS["fwd_q_" + name] += 1
+    return out
+
+
+def film_mean_q(xq: torch.Tensor, scale: Optional[torch.Tensor], gb: Optional[torch.Tensor], csr: GraphCSR,
+                mode="film_mean", logits: bool = False, out_dtype: torch.dtype = torch.bfloat16,
+                x0: Optional[torch.Tensor] = None, agg_scale: float = 1.0, x0_scale: float = 0.0) -> torch.Tensor:
+    """The FiLM-mean aggregation of FP8 messages, read natively (``mrp_film_mean_fwd_q``).
+
+    xq: (N, C, H, W) ``torch.float8_e4m3fn`` / ``torch.float8_e5m2`` codes; scale: their fp32 scales, (N,),
+    (N, 1) or (N, C) (``quantize_features``), or None; gb / csr / mode / logits as :func:`film_mean`.
+    Returns ``agg_scale * aggregate + x0_scale * x0`` in ``out_dtype`` (fp32, bf16 or fp16) — x0 (cast to
+    ``out_dtype``) carries a layer's own, unquantised features: a robot's own maps never cross the link.
+    Bit-equal to ``film_mean(dequantize_features(xq, scale), ...)`` with the same epilogue, cast once.
+    An inference op: under grad mode with a ``gb`` / ``x0`` that requires grad it raises (``film_mean_fq``
+    is the differentiable route)."""
+    if xq.dim() != 4:
+        raise ValueError(f"quantised features must be (N, C, H, W), got {tuple(xq.shape)}")
+    if out_dtype not in FEATURE_DTYPES:
+        raise TypeError(f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    out = torch.empty(xq.shape, device=xq.device, dtype=out_dtype)
+    return film_mean_q_forward_into(xq, scale, gb, csr, out, mode, logits, x0, agg_scale, x0_scale)
+
+
+class _StraightThrough(torch.autograd.Function):
+    """``xh`` in the forward (its bits untouched), the gradient handed to ``x`` as if ``xh`` were ``x``."""
+
+    @staticmethod
+    def forward(ctx, x, xh):
+        ctx.x_dtype = x.dtype
+        return xh.view_as(xh)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad.to(ctx.x_dtype), None
+
+
+def film_mean_fq(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, fmt: str = "e4m3",
+                 per: str = "channel", mode="film_mean", logits: bool = False, x0: Optional[torch.Tensor] = None,
+                 agg_scale: float = 1.0, x0_scale: float = 0.0) -> torch.Tensor:
+    """The differentiable fake-quant route of :func:`film_mean_q`, on the existing kernels: x is quantised
+    (``quantize_features``), x^ formed in fp32 (``dequantize_features``) with a straight-through estimator
+    (the gradient reaches x as if x^ = x), and the fp32 ``FilmMeanFunction`` run on it with the epilogue
+    (``x0.float()``); the result is cast to ``x.dtype``.  Its forward bits equal
+    ``film_mean_q(*quantize_features(x, fmt, per), ..., out_dtype=x.dtype)``."""
+    _check_x(x)
+    xq, s = quantize_features(x, fmt, per)
+    xh = dequantize_features(xq, s)
+    if torch.is_grad_enabled() and x.requires_grad:
+        xh = _StraightThrough.apply(x, xh)
+    m = _mode_flags(mode, logits)
+    if (m & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN:
+        gb = None
+    if x0 is not None:
+        # the native kernel reads x0 in the output type: the same value, widened exactly
+        x0 = x0.to(x.dtype).float()
+    out = FilmMeanFunction.apply(xh, gb, x0, csr, m, (float(agg_scale), 0.0, float(x0_scale) if x0 is not None else 0.0))
+    return out.to(x.dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Max-pooled FiLM aggregation: ``node_udf = torch.max(mailbox, 1)`` (``mrp_film_max_fwd`` / ``_bwd``).
 #
 #     m_j   = gamma_e * x[src(e)] + beta_e          for v's in-edges e in edge-id (mailbox) order

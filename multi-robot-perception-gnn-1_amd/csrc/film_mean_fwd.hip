@@ -26,9 +26,10 @@ int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float
                   const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs,
                   int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
                   int32_t mode_flags, void* out, int64_t out_node_stride, const mrp_agg_epilogue* ep, AggArgs& a,
-                  Geometry& g) {
+                  Geometry& g, size_t xelem) {
   g = Geometry();  // kernel = MRP_AGG_KERNEL_NONE until a launch is planned
   const bool half = elem == 2;  // 16-bit features (kHalfIo)
+  const bool quant = xelem != 0 && xelem != elem;  // FP8 messages: x holds 1-byte codes
   void* xcopy = ep != nullptr ? ep->xcopy : nullptr;
   const int64_t xcopy_node_stride = ep != nullptr ? ep->xcopy_node_stride : 0;
   const void* x0 = ep != nullptr ? ep->x0 : nullptr;
@@ -45,9 +46,9 @@ int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float
   if (mode != MRP_AGG_COPY_MEAN && num_edges > 0 && gb == nullptr) return hipErrorInvalidValue;
   if (xcopy != nullptr && xcopy_node_stride < plane) return hipErrorInvalidValue;
   if (x0 != nullptr && x0_node_stride < plane) return hipErrorInvalidValue;
-  SliceCheck sc;
-  sc.strides = P;
-  sc.add(x, x_node_stride);
+  SliceCheck sc, scx;  // scx: the 1-byte input of the FP8 path, checked at its own element size
+  sc.strides = scx.strides = P;
+  (quant ? scx : sc).add(x, x_node_stride);
   sc.add(out, out_node_stride);
   if (xcopy != nullptr) sc.add(xcopy, xcopy_node_stride);
   if (x0 != nullptr) sc.add(x0, x0_node_stride);
@@ -55,7 +56,13 @@ int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float
   const bool regular = kdeg >= 1 && kdeg <= 8;
   const Tuning& tu = tuning();
   int fvec, rvec;  // slice width of film_fwd / film_fwd_regular
-  if (half) {
+  if (quant) {
+    // the widest slice (elements) for which the codes (1 byte) and out / x0 (elem bytes) are both aligned:
+    // 8 (<= 8 nodes, 16-bit outputs: an 8-byte load, 16-byte stores), 4 (a 4-byte load, 8- or 16-byte
+    // stores), else single elements
+    const bool ok8 = elem == 2 && max_nodes <= 8 && scx.ok(8, xelem) && sc.ok(8, elem);
+    fvec = rvec = ok8 ? 8 : ((scx.ok(4, xelem) && sc.ok(4, elem)) ? 4 : 1);
+  } else if (half) {
     // 16-byte slices of 8 elements (graphs of <= 8 nodes: beyond, 8 slices of 16 sources are 128 live
     // registers before the first product), else 8-byte slices of 4, else single elements
     fvec = rvec = (max_nodes <= 8 && sc.ok(8, elem)) ? 8 : (sc.ok(4, elem) ? 4 : 1);

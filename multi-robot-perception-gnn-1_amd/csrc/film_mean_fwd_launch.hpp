@@ -122,14 +122,15 @@ struct SliceCheck {
 
 // The forward's launch plan (film_mean_fwd.hip): validation, kernel choice, slice width, geometry, plane
 // split and dynamic LDS for features of `elem` bytes per element.  No GPU call; the pointers are looked
-// at for alignment and NULL only.  Returns the code the entry points return before launching;
+// at for alignment and NULL only.  xelem: bytes per element of x where they differ from `elem` (1: the FP8
+// messages of film_mean_fwd_q.hip; 0: x holds `elem`-byte elements like every other feature tensor).  Returns the code the entry points return before launching;
 // g.kernel == MRP_AGG_KERNEL_NONE with hipSuccess: nothing to launch.  Behind both film_fwd_impl and
 // mrp_film_mean_fwd_plan.
 int film_fwd_plan(size_t elem, const void* x, int64_t x_node_stride, const float* gb, const int32_t* indptr,
                   const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs,
                   int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
                   int32_t mode_flags, void* out, int64_t out_node_stride, const mrp_agg_epilogue* ep, AggArgs& a,
-                  Geometry& g);
+                  Geometry& g, size_t xelem = 0);
 
 // The forward behind mrp_film_mean_fwd{,_ex,_t} and mrp_film_mean_cat_fwd; x, out and the epilogue's
 // x0 / xcopy hold elements of T, strides in elements.

@@ -86,6 +86,10 @@ struct AggArgs {
   const void* x0;
   int64_t x0s;
   int32_t nmax;  // max_nodes (COMPLETE graphs: every graph's node count)
+  // FP8 messages (film_fwd / film_fwd_regular with TX = q8_t): x holds 8-bit codes of format qfmt
+  // (mrp_qdtype), xscale (num_nodes, C) their per-(source node, channel) scales (NULL: all 1)
+  const float* xscale;
+  int32_t qfmt;
 };
 
 // Storage types of the feature tensors.  16-bit elements are widened exactly to fp32 on load and
@@ -139,6 +143,56 @@ __device__ __forceinline__ void store_frag16(T* p, const Frag<VEC>& f) {
     else
       *reinterpret_cast<tv*>(p) = t;
   }
+}
+
+// 8-bit storage of the gathered messages: one OCP FP8 code per element — E4M3 (torch.float8_e4m3fn: no
+// infinities, NaN = 0x7f / 0xff, max 448) or E5M2 (torch.float8_e5m2: IEEE-like, max 57344); never the
+// FNUZ encodings.  Input only: nothing is stored in it.
+struct q8_t {
+  uint8_t b;
+};
+
+// A slice of VEC codes as one nontemporal access of VEC bytes (VEC 8 / 4 / 1), decoded exactly by the
+// hardware conversions (v_cvt_pk_f32_fp8 / _bf8: subnormals, NaN and inf codes included) and multiplied
+// once by the source's scale: x^ = fl32(s * decode(q)).  fmt (mrp_qdtype) is wave-uniform.
+template <int VEC, bool NTL>
+__device__ __forceinline__ Frag<VEC> load_frag(const q8_t* p, int fmt, float s) {
+  static_assert(VEC == 8 || VEC == 4 || VEC == 1, "8-bit slices: 8, 4 or 1 bytes");
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  constexpr int NW = VEC == 8 ? 2 : 1;
+  uint32_t w[NW];
+  if constexpr (VEC == 8) {
+    const u2* q = reinterpret_cast<const u2*>(p);
+    const u2 t = NTL ? __builtin_nontemporal_load(q) : *q;
+    w[0] = t.x;
+    w[1] = t.y;
+  } else if constexpr (VEC == 4) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+    w[0] = NTL ? __builtin_nontemporal_load(q) : *q;
+  } else {
+    w[0] = NTL ? __builtin_nontemporal_load(&p->b) : p->b;
+  }
+  Frag<VEC> f;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    f2 lo, hi;
+    if (fmt == MRP_QDTYPE_E5M2) {
+      lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)w[i], false);
+      hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)w[i], true);
+    } else {
+      lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+      hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    }
+    if constexpr (VEC == 1) {
+      f.v[0] = __fmul_rn(s, lo.x);
+    } else {
+      f.v[4 * i + 0] = __fmul_rn(s, lo.x);
+      f.v[4 * i + 1] = __fmul_rn(s, lo.y);
+      f.v[4 * i + 2] = __fmul_rn(s, hi.x);
+      f.v[4 * i + 3] = __fmul_rn(s, hi.y);
+    }
+  }
+  return f;
 }
 
 template <int VEC, bool NTL>
@@ -515,10 +569,13 @@ __device__ __forceinline__ void complete_rest(const AggArgs& a, int64_t ebase, i
 // N <= 8): no per-term select between the modes, and the mean's division by N - 1 as the exact
 // three-instruction quotient (fast_math.hpp) for a whole slice at once.  MODE = -1: mode at run time.
 // T: the feature tensors' storage type (float, bf16_t, f16_t); VEC counts elements of T.
-template <int NT, int VEC, bool COMPLETE, int MODE = -1, typename T = float>
+// TX: the storage type of the gathered input x alone (out, x0 and xcopy keep T).  TX = q8_t: FP8 messages,
+// widened and scaled in load_frag (a.qfmt, a.xscale); the arithmetic from there on is TX = T's.
+template <int NT, int VEC, bool COMPLETE, int MODE = -1, typename T = float, typename TX = T>
 __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
   constexpr int SZ = Tile<NT>::SZ;
   constexpr int NTP = Tile<NT>::NTP;
+  constexpr bool kQ = std::is_same<TX, q8_t>::value;
   constexpr bool kBatchDiv = COMPLETE && MODE == MRP_AGG_FILM_MEAN && NT >= 2;
   extern __shared__ float4 smem_f4[];
   float* smem = reinterpret_cast<float*>(smem_f4);
@@ -549,9 +606,19 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  const TX* xb = static_cast<const TX*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
   T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
   const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
+  const uint32_t lane_plane_x = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(TX);
+  // FP8 messages: the scales of this lane's channel for the graph's nodes, read once per workgroup
+  float xsc[kQ ? NT : 1];
+  if constexpr (kQ) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int uu = u < n ? u : n - 1;
+      xsc[u] = (active && a.xscale != nullptr) ? a.xscale[(int64_t)(node0 + uu) * a.C + c] : 1.f;
+    }
+  }
 
   // prologue part 1 (COMPLETE): gamma/beta into registers
   float2 reg[CompleteSlots<NT>::kPer];
@@ -568,7 +635,12 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       const int uu = u < n ? u : n - 1;  // clamp (ragged batch); never used for output
-      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * (uint32_t)sizeof(T)));
+      const TX* px = at_bytes(xb + (int64_t)uu * a.xs, lane_plane_x + (uint32_t)jj * VEC * (uint32_t)sizeof(TX));
+      Frag<VEC> f;
+      if constexpr (kQ)
+        f = load_frag<VEC, true>(px, a.qfmt, xsc[u]);
+      else
+        f = load_frag<VEC, true>(px);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) xv[k][u] = f.v[k];
     }
@@ -694,7 +766,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
       store_frag<VEC, true>(at_bytes(ob + (int64_t)v * a.os, lane_off), acc);
     }
 
-    if (a.xc != nullptr) {
+    if (!kQ && a.xc != nullptr) {
       // cat((x, aggregate), 1): the slices of x are in registers already; writing them here saves
       // the separate copy's read of x
       T* xcb = static_cast<T*>(a.xc) + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
@@ -729,9 +801,11 @@ __global__ void __launch_bounds__(kBlock) film_fwd(AggArgs a) {
 // the mode is a mean: the slot loop has no exit test and the mean's division is the exact product
 // by 1/KC (x * 2^-k is the correctly rounded x / 2^k), instead of the ~10-instruction IEEE division
 // per destination and element.  KC = 0: runtime K and mode.
-template <int NT, int KMAX, int VEC, int KC = 0, typename T = float>
+// TX: the gathered input's storage type, as in film_fwd.
+template <int NT, int KMAX, int VEC, int KC = 0, typename T = float, typename TX = T>
 __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
   static_assert(KC == 0 || (KC <= KMAX && (KC & (KC - 1)) == 0), "compile-time degree: a power of two");
+  constexpr bool kQ = std::is_same<TX, q8_t>::value;
   constexpr int NS = NT * KMAX;
   constexpr int WS = NS + 2;     // per-channel stride of the slot weights (float2), padded 4 banks
   constexpr int WPD = KMAX / 4;  // 32-bit words of packed 8-bit slot sources per destination
@@ -759,9 +833,19 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
   // uniform per-graph/channel-block bases, per-lane 32-bit byte offsets (see at_bytes)
-  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  const TX* xb = static_cast<const TX*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
   T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
   const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
+  const uint32_t lane_plane_x = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(TX);
+  // FP8 messages: the scales of this lane's channel for the graph's nodes, read once per workgroup
+  float xsc[kQ ? NT : 1];
+  if constexpr (kQ) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int uu = u < n ? u : n - 1;
+      xsc[u] = (active && a.xscale != nullptr) ? a.xscale[(int64_t)(node0 + uu) * a.C + c] : 1.f;
+    }
+  }
 
   // First slice's loads, issued before the prologue's two dependent rounds.  Element k of every
   // source's slice lives in one NT-wide vector value, so the wave-uniform source index is a dynamic
@@ -773,7 +857,12 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       const int uu = u < n ? u : n - 1;
-      const Frag<VEC> f = load_frag<VEC, true>(at_bytes(xb + (int64_t)uu * a.xs, lane_plane + (uint32_t)jj * VEC * (uint32_t)sizeof(T)));
+      const TX* px = at_bytes(xb + (int64_t)uu * a.xs, lane_plane_x + (uint32_t)jj * VEC * (uint32_t)sizeof(TX));
+      Frag<VEC> f;
+      if constexpr (kQ)
+        f = load_frag<VEC, true>(px, a.qfmt, xsc[u]);
+      else
+        f = load_frag<VEC, true>(px);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) xs[k][u] = f.v[k];
     }
@@ -906,7 +995,7 @@ __global__ void __launch_bounds__(kBlock) film_fwd_regular(AggArgs a) {
         store_frag<VEC, true>(at_bytes(ob + (int64_t)v * a.os, lane_off), o);
       }
     }
-    if (a.xc != nullptr) {
+    if (!kQ && a.xc != nullptr) {
       T* xcb = static_cast<T*>(a.xc) + (int64_t)node0 * a.xcs + (int64_t)c0 * a.P;
 #pragma unroll
       for (int u = 0; u < NT; ++u) {

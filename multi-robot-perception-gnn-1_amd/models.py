@@ -28,6 +28,14 @@ Semantics switch ``opt.gcn_return``:
 ``torch.max(mailbox, 1)``: :func:`aggregate.film_max`, every in-degree <= 16), ``'film_attn'`` (per-location
 attention over the messages: :func:`aggregate.film_attn`, every in-degree <= 16; ``opt.gcn_attn_scale``
 sets the score scale, default ``None``: 1/sqrt(C)).
+
+``opt.gcn_message_dtype``: ``None`` (default: nothing changes), ``'fp8_e4m3'`` or ``'fp8_e5m2'`` — the
+feature maps every GCN layer aggregates are quantised per node to OCP FP8, as each robot would transmit them
+over an 8-bit link, with one scale per (node, channel) (``opt.gcn_message_scale='channel'``, the default) or
+per node (``'node'``); the layer's own-feature terms (cat half, residual, compress input) use the
+unquantised features.  In a single-GPU simulation the quantise pass costs more than the aggregation saves:
+the option exists to evaluate and train models for 8-bit links.  The saving belongs to a receiver that is
+handed FP8 buffers (:func:`aggregate.film_mean_q`).  See :meth:`GCN._aggregate_q`.
 """
 from __future__ import annotations
 
@@ -36,9 +44,10 @@ import warnings
 import torch
 import torch.nn as nn
 
+from .aggregate import (film_mean_fq, film_mean_q, film_mean_q_forward_into, quantize_features)
 from .aggregate import (film_attn, film_attn_cat, film_attn_mix, film_attn_residual, film_max, film_max_cat,
                         film_max_mix, film_max_residual, film_mean, film_mean_cat, film_mean_mix, film_mean_residual)
-from .compress import compress_1x1, compress_path, film_compress, film_compress_supported
+from .compress import CompressFunction, compress_1x1, compress_path, film_compress, film_compress_supported
 from .encoder import edge_logits
 
 
@@ -105,6 +114,23 @@ def _opt(opt, name, default):
     return getattr(opt, name, default) if opt is not None else default
 
 
+#: ``opt.gcn_message_dtype`` -> the FP8 format of the aggregated messages (``aggregate.QUANT_FORMATS``)
+MESSAGE_DTYPES = {None: None, "fp8_e4m3": "e4m3", "fp8_e5m2": "e5m2"}
+MESSAGE_SCALES = ("channel", "node")
+
+
+def message_format(opt):
+    """(FP8 format or None, scale granularity) from ``opt.gcn_message_dtype`` / ``opt.gcn_message_scale``;
+    an unknown value is a ``ValueError`` (raised when a module is built)."""
+    dtype = _opt(opt, "gcn_message_dtype", None)
+    per = _opt(opt, "gcn_message_scale", "channel")
+    if dtype not in MESSAGE_DTYPES:
+        raise ValueError(f"gcn_message_dtype must be one of {tuple(MESSAGE_DTYPES)}, got {dtype!r}")
+    if per not in MESSAGE_SCALES:
+        raise ValueError(f"gcn_message_scale must be one of {MESSAGE_SCALES}, got {per!r}")
+    return MESSAGE_DTYPES[dtype], per
+
+
 #: ``gcn_return`` given to a GCN unpickled from a reference checkpoint whose ``opt`` has none (see
 #: :meth:`GCN.__setstate__`); ``compat.reference_class_path(gcn_return=...)`` sets it.
 UNPICKLED_GCN_RETURN = "input"
@@ -116,6 +142,7 @@ class GCN(_PackedImages, nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
+        message_format(opt)  # an unknown gcn_message_dtype / gcn_message_scale: ValueError here
         self.edge_encoder = edge_encoder(layers_dim=[opt.feature_dim, opt.feature_dim])
         # marks a GCN this framework built: its pickles (deepcopy, torch.save of the whole model as the
         # reference's training.py:345-355 does) keep computing the aggregate
@@ -143,10 +170,37 @@ class GCN(_PackedImages, nn.Module):
         """``opt.gcn_attn_scale``: the score scale of ``gcn_mode='film_attn'`` (None: 1/sqrt(C))."""
         return _opt(self.opt, "gcn_attn_scale", None)
 
+    def _aggregate_q(self, g, x, fmt, per, x0=None, agg_scale=1.0, x0_scale=0.0, out=None):
+        """``agg_scale * aggregate(quantised x) + x0_scale * x0`` for ``opt.gcn_message_dtype``, in x's
+        dtype.  Grad mode off and CUDA features: ``quantize_features`` + the native FP8 kernel
+        (``film_mean_q``; into ``out`` if given).  Grad mode on: the fake-quant route ``film_mean_fq`` on the
+        fp32 kernels, straight-through to x.  Both return the same bits.  In a single-GPU simulation the
+        quantise pass costs more than the aggregation saves; the option is for evaluating and training
+        models for 8-bit links, and the saving belongs to a receiver that is handed FP8 buffers."""
+        mode = _opt(self.opt, "gcn_mode", "film_mean")
+        if mode in ("film_max", "film_attn"):
+            raise ValueError(f"gcn_message_dtype is not provided for gcn_mode={mode!r} (film_mean, film_sum, copy_mean)")
+        if self._return_mode() == "input":
+            raise ValueError("gcn_message_dtype with gcn_return='input': no message is aggregated")
+        csr = g.csr(x.device)
+        z = None if mode == "copy_mean" else self.edge_encoder.logits(g.edata["pose"])
+        if x.is_cuda and not torch.is_grad_enabled():
+            xq, s = quantize_features(x, fmt, per)
+            if out is None:
+                return film_mean_q(xq, s, z, csr, mode, logits=True, out_dtype=x.dtype, x0=x0, agg_scale=agg_scale,
+                                   x0_scale=x0_scale)
+            return film_mean_q_forward_into(xq, s, z, csr, out, mode, logits=True, x0=x0, agg_scale=agg_scale,
+                                            x0_scale=x0_scale)
+        a = film_mean_fq(x, z, csr, fmt, per, mode, logits=True, x0=x0, agg_scale=agg_scale, x0_scale=x0_scale)
+        return a if out is None else out.copy_(a)
+
     def forward(self, g, feats: torch.Tensor = None) -> torch.Tensor:
         """The aggregate of ``feats`` (fp32, bf16 or fp16; returned in that dtype — the encoder's logits
         stay fp32 and the aggregation's arithmetic is fp32 either way)."""
         x = g.ndata["image"] if feats is None else feats
+        fmt, per = message_format(self.opt)
+        if fmt is not None:
+            return self._aggregate_q(g, x, fmt, per)
         if self._return_mode() == "input":
             return x  # models.py:226 returns the input; update_all's result is never read
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -164,6 +218,15 @@ class GCN(_PackedImages, nn.Module):
         """``torch.cat((feats, self(g, feats)), 1)`` (``models.py:181-182``) with the aggregate written
         straight into the concatenation buffer (and the backward fused likewise)."""
         x = g.ndata["image"] if feats is None else feats
+        fmt, per = message_format(self.opt)
+        if fmt is not None:
+            if torch.is_grad_enabled() or not x.is_cuda:
+                return torch.cat((x, self._aggregate_q(g, x, fmt, per)), dim=1)
+            n, C, H, W = x.shape  # the aggregate straight into the buffer's second half, one copy of x
+            cat = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+            self._aggregate_q(g, x, fmt, per, out=cat[:, C:])
+            cat[:, :C].copy_(x)
+            return cat
         if self._return_mode() == "input" or not x.is_cuda:
             return torch.cat((x, self(g, x)), dim=1)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -195,6 +258,14 @@ class GCN(_PackedImages, nn.Module):
         features do the same after ``compress.set_channels_last_compress_fp32('native')``
         (``compress_split_cl.hip``; by default they are copied to NCHW and the layer returns NCHW)."""
         x = feats
+        fmt, per = message_format(self.opt)
+        if fmt is not None:
+            # the aggregate of the quantised messages into its own buffer, then the compress kernels on
+            # (x, aggregate) with no concatenation; x itself stays unquantised
+            a = self._aggregate_q(g, x, fmt, per)
+            if x.is_cuda and film_compress_supported(conv, x):
+                return CompressFunction.apply(x, a, conv.weight, conv.bias)
+            return compress_1x1(conv, torch.cat((x, a), dim=1))
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):
             mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -213,6 +284,9 @@ class GCN(_PackedImages, nn.Module):
         """``feats + self(g, feats)`` in one kernel pass: the residual combination ``h = g_h + h``
         of ``dgl/model/dgl_models.py:36-37`` (the FiLM-mean 'add' variant)."""
         x = g.ndata["image"] if feats is None else feats
+        fmt, per = message_format(self.opt)
+        if fmt is not None:  # the layer's own h through the epilogue's x0, unquantised
+            return self._aggregate_q(g, x, fmt, per, x0=x, x0_scale=1.0)
         if self._return_mode() == "input" or not x.is_cuda:
             return x + self(g, x)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -229,6 +303,9 @@ class GCN(_PackedImages, nn.Module):
         """``(1 - alpha) * self(g, feats) + alpha * x0`` in one kernel pass: a GCN2-style
         initial-feature mix (BASELINE configs[3]'s "GCN2Conv"; not in the reference)."""
         x = feats
+        fmt, per = message_format(self.opt)
+        if fmt is not None:
+            return self._aggregate_q(g, x, fmt, per, x0=x0, agg_scale=1.0 - float(alpha), x0_scale=float(alpha))
         if self._return_mode() == "input" or not x.is_cuda:
             return (1.0 - alpha) * self(g, x) + alpha * x0
         mode = _opt(self.opt, "gcn_mode", "film_mean")

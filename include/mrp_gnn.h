@@ -568,6 +568,101 @@ int64_t mrp_film_attn_workspace(int32_t direction, int32_t num_graphs, int32_t m
                                 int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
 
 /*
+ * The confidence-weighted FiLM aggregation (ABI 22, extended): every sender u attaches a per-pixel map
+ * w[u,p] >= 0 to its feature map (where in the image it transmits), and the receiver averages, pixel by pixel,
+ * over what was delivered there.  An operator of its own with its own kernels (the mean's channel-block-major
+ * decomposition); every other entry point is unchanged.
+ *
+ *   x   (num_nodes, C, P) of `dtype`, node stride x_node_stride
+ *   gb  (num_edges, C, 2) fp32 interleaved gamma/beta, or their logits with MRP_AGG_GB_LOGITS
+ *   w   (num_nodes, P) fp32, node stride w_node_stride >= P, indexed by SOURCE node
+ *   the graph arguments exactly as mrp_film_max_fwd (every kind, max_nodes <= MRP_MAX_NODES)
+ *
+ * Forward.  For destination v with row entries j in row order (edge-id order), e_j the edge and u_j the source:
+ *
+ *   m_j[c,p]   = fl(fl(gamma_{e_j}[c] * x[u_j,c,p]) + beta_{e_j}[c])        no FMA contraction (as the mean)
+ *   acc[v,c,p] = sum_j in row order  fl(acc + fl(w[u_j,p] * m_j[c,p]))
+ *   D[v,p]     = sum_j in row order  fl(D + w[u_j,p])
+ *   out[v,c,p] = D[v,p] > 0 ? acc / D (IEEE division) : 0                    MRP_WAGG_MEAN
+ *   out[v,c,p] = acc[v,c,p]                                                  MRP_WAGG_SUM
+ *
+ * An empty row, or a pixel at which every sender is silent, gives an exact 0 (the mean's zero fill).
+ * Order of the sums: exactly the mean forward's, so that the two operators can be compared bit for bit.  The
+ * kernels sum a destination's sources in ascending source order, and parallel edges u -> v are one term,
+ * fl(w[u,p] * fl(fl(G x) + B)) with G, B the sums of the edges' gamma, beta in row order and
+ * fl(cnt * w[u,p]) in D.  That is the row-order chain above whenever a row is in ascending source order
+ * without parallel edges (complete i-major graphs, the k-NN and range builders): the condition under which
+ * the mean itself keeps the reference's rounding order.  Consequences, for every graph:
+ *   - w == 1 gives mrp_film_mean_fwd_t's bits in modes film_mean / film_sum (fl(1 * m) = m, D the in-degree);
+ *   - a 0/1 map constant over each node's plane gives film_mean's bits on the graph without the silent
+ *     robots' out-edges.
+ *
+ * Backward.  Gh[v,c,p] = grad_out / D where D > 0 and 0 elsewhere (MEAN), grad_out (SUM):
+ *
+ *   grad_x[u,c,p]  = w[u,p] * sum over (v,j) with u_j = u of gamma_{e_j}[c] * Gh[v,c,p]    (+ grad_x_base)
+ *   grad_gb[e,c,0] = sum_p w[u,p] * x[u,c,p] * Gh[v,c,p]
+ *   grad_gb[e,c,1] = sum_p w[u,p] * Gh[v,c,p]
+ *   grad_w[u,p]    = sum over (v,j) with u_j = u, sum_c Gh[v,c,p] * (m_j[c,p] - out[v,c,p])   MEAN
+ *   grad_w[u,p]    = sum over (v,j) with u_j = u, sum_c grad_out[v,c,p] * m_j[c,p]            SUM
+ *
+ * The backward recomputes `out` from x, gb and w with the forward's arithmetic; it takes no saved output.
+ * With MRP_AGG_GB_LOGITS grad_gb is d logits.  grad_x, grad_gb and grad_w (fp32, node stride gw_node_stride
+ * >= P) may each be NULL to skip that output; all NULL returns success without a launch.  grad_gb rows no CSR
+ * entry names are written as zeros.  Sums: grad_x over destinations ascending; grad_gb per lane over its
+ * slices, then a fixed butterfly over the plane's lanes; grad_w over channels ascending within a block of 16
+ * channels (destinations ascending inside), the blocks' partials then added in block order from `workspace`.
+ *
+ * 16-bit features: widened exactly on load, the fp32 arithmetic above unchanged, one round-to-nearest-even at
+ * each store of T; w, gamma/beta, grad_gb and grad_w stay fp32: fwd(T, x) == T(fwd(float(x))) bit for bit
+ * (the per-element sums do not depend on slice width or geometry).
+ *
+ * Determinism: no atomics, one writer per output element, every sum in an order fixed by the shapes and the
+ * graph.  No allocation, no host synchronisation, capturable (a hipMemsetAsync of grad_gb precedes the kernels
+ * of non-COMPLETE graphs).  64-bit node offsets.
+ *
+ * Preconditions: w finite and >= 0.  Negative weights run the arithmetic above without an accuracy promise.  A
+ * NaN or infinity in w[u,p] reaches `out` of the destinations that consume u, at pixel p, and nothing else.
+ *
+ * mrp_film_wmean_workspace is the byte count `workspace` must hold where grad_w is wanted: the per-block
+ * partials (ceil(C / 16) x num_nodes x P floats) when C > 16, else 0.  It makes no GPU call.
+ * Validation precedes any launch and matches mrp_film_max_*; in addition hipErrorInvalidValue is returned for a
+ * NULL w with work to do, w_node_stride < P (gw_node_stride < P), an unknown wagg mode, and a workspace
+ * smaller than needed.  Empty work returns success.  out_node_stride / g_node_stride let the aggregate and
+ * its gradient be the second half of a concatenation buffer.
+ */
+enum mrp_wagg_mode { MRP_WAGG_MEAN = 0, MRP_WAGG_SUM = 1 };
+
+int mrp_film_wmean_fwd(int32_t dtype,
+                       const void* x, int64_t x_node_stride,
+                       const float* gb,
+                       const float* w, int64_t w_node_stride,
+                       const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                       const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                       int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                       int32_t C, int32_t P, int32_t flags, int32_t wagg,
+                       void* out, int64_t out_node_stride,
+                       void* stream);
+
+int mrp_film_wmean_bwd(int32_t dtype,
+                       const void* grad_out, int64_t g_node_stride,
+                       const void* x, int64_t x_node_stride,
+                       const float* gb,
+                       const float* w, int64_t w_node_stride,
+                       const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                       const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                       int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                       int32_t C, int32_t P, int32_t flags, int32_t wagg,
+                       void* grad_x, int64_t gx_node_stride,
+                       const void* grad_x_base, int64_t base_node_stride,
+                       float* grad_gb,
+                       float* grad_w, int64_t gw_node_stride,
+                       void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+int64_t mrp_film_wmean_workspace(int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                 int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

@@ -14,6 +14,8 @@ from .aggregate import (dequantize_features, film_mean_fq, film_mean_q, film_mea
                         quantize_features)
 from .aggregate import (FilmMaxFunction, film_max, film_max_backward, film_max_cat,  # noqa: F401
                         film_max_forward_into)
+from .aggregate import (FilmWMeanCatFunction, FilmWMeanFunction, film_wmean, film_wmean_backward,  # noqa: F401
+                        film_wmean_cat, film_wmean_forward_into, film_wmean_mix, film_wmean_residual)
 from .aggregate import (FilmAttnCatFunction, FilmAttnFunction, film_attn, film_attn_backward,  # noqa: F401
                         film_attn_cat, film_attn_forward_into, film_attn_mix, film_attn_residual)
 from . import compat, compress, encoder  # noqa: F401

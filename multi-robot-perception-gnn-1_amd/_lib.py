@@ -39,6 +39,9 @@ EXPORTED_SYMBOLS = (
     "mrp_film_attn_fwd",
     "mrp_film_attn_bwd",
     "mrp_film_attn_workspace",
+    "mrp_film_wmean_fwd",
+    "mrp_film_wmean_bwd",
+    "mrp_film_wmean_workspace",
     "mrp_compress_fwd",
     "mrp_compress_weight_transpose",
     "mrp_compress_bwd_data",
@@ -97,6 +100,8 @@ ABI_VERSION = 22
 MAX_NODES = 16
 FILM_MAX_DEGREE = 16  # MRP_FILM_MAX_DEGREE: largest in-degree of the max-pooled aggregation
 FILM_ATTN_DEGREE = 16  # MRP_FILM_ATTN_DEGREE: largest in-degree of the attention-pooled aggregation
+WAGG_MEAN = 0  # enum mrp_wagg_mode: the confidence-weighted aggregation's normalised / plain weighted sum
+WAGG_SUM = 1
 
 HIP_ERROR_NOT_SUPPORTED = 801  # hipErrorNotSupported: a fused path declines this shape
 
@@ -213,6 +218,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_attn_bwd.restype = ctypes.c_int
     lib.mrp_film_attn_workspace.argtypes = [_I32] * 8
     lib.mrp_film_attn_workspace.restype = ctypes.c_int64
+    # the confidence-weighted aggregation: (w, w_node_stride) follow gb, wagg follows flags; the backward
+    # ends with grad_w, gw_node_stride, workspace, workspace_bytes, stream
+    lib.mrp_film_wmean_fwd.argtypes = [_I32, _P, _I64, _P, _P, _I64] + graph[:-1] + [_I32, _I32, _P, _I64, _P]
+    lib.mrp_film_wmean_fwd.restype = ctypes.c_int
+    lib.mrp_film_wmean_bwd.argtypes = ([_I32, _P, _I64, _P, _I64, _P, _P, _I64] + graph[:-1] +
+                                       [_I32, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P])
+    lib.mrp_film_wmean_bwd.restype = ctypes.c_int
+    lib.mrp_film_wmean_workspace.argtypes = [_I32] * 7
+    lib.mrp_film_wmean_workspace.restype = ctypes.c_int64
     lib.mrp_tuning_set.argtypes = [ctypes.c_char_p, _I32]
     lib.mrp_tuning_set.restype = ctypes.c_int
     lib.mrp_compress_fwd.argtypes = [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _I64, _P]

@@ -1185,3 +1185,228 @@ def film_attn_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Te
                   logits: bool = False, scale: Optional[float] = None) -> torch.Tensor:
     """``(1 - alpha) * film_attn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
     return (1.0 - float(alpha)) * film_attn(x, gb, csr, logits, scale) + float(alpha) * x0
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Confidence-weighted FiLM aggregation: per-pixel sender maps (``mrp_film_wmean_fwd`` / ``_bwd``).
+#
+#     m_j   = gamma_e * x[src(e)] + beta_e                      for v's in-edges e
+#     out_v = sum_j w[src(e_j)] * m_j / sum_j w[src(e_j)]       pixel by pixel; 0 where nobody delivered
+#
+# ``w`` (N, H, W) fp32 >= 0 is the sender's spatial confidence map (Where2comm-style sparse messaging): a
+# sender transmits only the locations worth sending and the receiver averages over what arrived.  With
+# ``mode="sum"`` the weighted sum is not normalised.  An operator of its own with gradients for x, gb and w;
+# with w == 1 it gives ``film_mean``'s bits.  channels_last features take the copy-first route.
+# ---------------------------------------------------------------------------------------------------------
+WAGG_MODES = {"mean": _lib.WAGG_MEAN, "sum": _lib.WAGG_SUM}
+
+
+def _wagg(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in WAGG_MODES:
+            raise ValueError(f'film_wmean mode must be "mean" or "sum", got {mode!r}')
+        return WAGG_MODES[mode]
+    mode = int(mode)
+    if mode not in WAGG_MODES.values():
+        raise ValueError(f"film_wmean mode must be WAGG_MEAN or WAGG_SUM, got {mode}")
+    return mode
+
+
+def _check_wmean_flags(flags: int) -> int:
+    flags = int(flags)
+    if flags not in (0, _lib.GB_LOGITS):
+        raise ValueError(f"film_wmean flags must be 0 or GB_LOGITS ({_lib.GB_LOGITS:#x}), got {flags:#x}")
+    return flags
+
+
+def _wmean_weights(w: torch.Tensor, n: int, H: int, W: int):
+    """(w, node stride in elements) of a sender map (N, H, W) or (N, 1, H, W): fp32, each node's plane
+    contiguous, the planes ``>= H*W`` apart."""
+    if w is None:
+        raise ValueError("film_wmean needs the sender maps w (N, H, W)")
+    _require_device(w)
+    if w.dim() == 4 and w.shape[1] == 1:
+        w = w[:, 0]
+    if w.dim() != 3 or tuple(w.shape) != (n, H, W):
+        raise ValueError(f"w must be {(n, H, W)} or {(n, 1, H, W)}, got {tuple(w.shape)}")
+    if w.dtype != torch.float32:
+        raise ValueError(f"w must be float32, got {w.dtype}")
+    s = w.stride()
+    P = H * W
+    ok = n == 0 or P == 0 or ((W == 1 or s[2] == 1) and (H == 1 or s[1] == W) and (n == 1 or s[0] >= P))
+    if not ok:
+        raise ValueError("w must have a contiguous (H, W) plane per node")
+    return w, (s[0] if n > 1 else P)
+
+
+def film_wmean_forward_into(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, flags: int,
+                            out: torch.Tensor, mode="mean") -> torch.Tensor:
+    """Run ``mrp_film_wmean_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
+    half of a ``torch.cat((h, g_h), 1)`` buffer.  ``flags``: 0 or ``_lib.GB_LOGITS``.  No autograd."""
+    _require_device(x, out)
+    flags, wagg = _check_wmean_flags(flags), _wagg(mode)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
+    os_ = node_stride(out)
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    w, ws = _wmean_weights(w, n, H, W)
+    gb = _max_gb(gb, csr, C)
+    ga = _graph_args(gb, csr, C, H * W, flags)
+    lib = _lib.load_library()
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_wmean_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, ga[0], _ptr(w), ws, *ga[1:], wagg,
+                                      _ptr(out), os_, _stream(x.device))
+    _lib.check(code, "mrp_film_wmean_fwd")
+    PATH_COUNTS["wmean_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+    return out
+
+
+def film_wmean_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR,
+                        flags: int, need_dx: bool, need_dgb: bool, need_dw: bool,
+                        grad_x_base: Optional[torch.Tensor] = None, mode="mean"):
+    """(grad_x, grad_gb (E, C, 2), grad_w (N, H, W)) of :func:`film_wmean_forward_into`, each None unless
+    asked for; ``grad_x_base`` (N, C, H, W), if given, is added into grad_x by the kernel.  The kernels
+    recompute the aggregate (nothing is saved by the forward); grad_x is NCHW in x's dtype, grad_gb and grad_w
+    are fp32."""
+    _require_device(grad_out, x)
+    flags, wagg = _check_wmean_flags(flags), _wagg(mode)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    # the kernel reads grad_out and the base with x's extents: a mismatch would be an out-of-bounds read
+    if tuple(grad_out.shape) != (n, C, H, W):
+        raise ValueError(f"grad_out must be {(n, C, H, W)}, got {tuple(grad_out.shape)}")
+    if grad_x_base is not None and tuple(grad_x_base.shape) != (n, C, H, W):
+        raise ValueError(f"grad_x_base must be {(n, C, H, W)}, got {tuple(grad_x_base.shape)}")
+    if grad_x_base is not None:
+        _require_device(grad_x_base)
+    w, ws = _wmean_weights(w, n, H, W)
+    if not (need_dx or need_dgb or need_dw):
+        return None, None, None
+    dtype = x.dtype
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
+    grad_out, gs = _as_node_major(grad_out)
+    x, xs = _as_node_major(x)
+    bs = 0
+    if grad_x_base is not None and need_dx:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
+        grad_x_base, bs = _as_node_major(grad_x_base)
+    else:
+        grad_x_base = None
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
+    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    dw = torch.empty((n, H, W), device=x.device, dtype=torch.float32) if need_dw else None
+    gb = _max_gb(gb, csr, C)
+    ga = _graph_args(gb, csr, C, H * W, flags)
+    lib = _lib.load_library()
+    work, nbytes = None, 0
+    if need_dw:
+        nbytes = lib.mrp_film_wmean_workspace(csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes,
+                                              csr.num_edges, C, H * W)
+        if nbytes > 0:
+            work = torch.empty(((nbytes + 3) // 4,), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_wmean_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, ga[0], _ptr(w), ws,
+                                      *ga[1:], wagg, _ptr(dx), (C * H * W) if dx is not None else 0,
+                                      _ptr(grad_x_base), bs, _ptr(dgb), _ptr(dw), H * W if dw is not None else 0,
+                                      _ptr(work), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_wmean_bwd")
+    PATH_COUNTS["wmean_bwd_" + _DTYPE_KEYS[dtype]] += 1
+    return dx, dgb, dw
+
+
+class FilmWMeanFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = ``mrp_film_wmean_fwd``, backward = ``mrp_film_wmean_bwd`` with gradients
+    for x, gb and w.  ``flags`` may be ``_lib.GB_LOGITS`` (the gb gradient is then d logits)."""
+
+    @staticmethod
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, wagg: int):
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+        film_wmean_forward_into(x, gb, w, csr, flags, out, wagg)
+        ctx.save_for_backward(x, gb, w)
+        ctx.csr, ctx.flags, ctx.wagg = csr, flags, wagg
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gb, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgb, dw = film_wmean_backward(grad_out, x, gb, w, ctx.csr, ctx.flags, need[0], need[1], need[2],
+                                          mode=ctx.wagg)
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        if dw is not None:
+            dw = dw.view(w.shape)
+        return dx, dgb, dw, None, None, None
+
+
+def film_wmean(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, mode="mean",
+               logits: bool = False) -> torch.Tensor:
+    """``sum_e w[src e] (gamma_e * x_src + beta_e) / sum_e w[src e]`` per destination node and pixel
+    (``mode="sum"``: the numerator alone); pixels nobody delivered to give 0.  Differentiable in x, gb and w.
+
+    x: (N, C, H, W) fp32, bf16 or fp16 on a ROCm device; gb: (E, 2C) or (E, C, 2) interleaved gamma/beta, or
+    their pre-sigmoid logits with ``logits=True``; w: (N, H, W) or (N, 1, H, W) fp32 >= 0, each node's plane
+    contiguous — the sender's map, indexed by source node; csr: ``RobotGraph.csr(device)``."""
+    wagg = _wagg(mode)  # a host-side argument: checked before anything touches a device
+    _check_x(x)
+    return FilmWMeanFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, wagg)
+
+
+class FilmWMeanCatFunction(torch.autograd.Function):
+    """``torch.cat((x, film_wmean(x, gb, w)), 1)``: the kernel writes the aggregate into the second half of
+    the (N, 2C, H, W) buffer through its node stride, x is copied into the first half by torch; backward hands
+    the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
+
+    @staticmethod
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, wagg: int):
+        n, C, H, W = x.shape
+        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        film_wmean_forward_into(x, gb, w, csr, flags, buf[:, C:], wagg)
+        buf[:, :C].copy_(x)
+        ctx.save_for_backward(x, gb, w)
+        ctx.csr, ctx.flags, ctx.wagg = csr, flags, wagg
+        return buf
+
+    @staticmethod
+    def backward(ctx, grad_buf):
+        x, gb, w = ctx.saved_tensors
+        C = x.shape[1]
+        need = ctx.needs_input_grad
+        dx, dgb, dw = film_wmean_backward(grad_buf[:, C:], x, gb, w, ctx.csr, ctx.flags, need[0], need[1], need[2],
+                                          grad_x_base=grad_buf[:, :C] if need[0] else None, mode=ctx.wagg)
+        if dgb is not None:
+            dgb = dgb.view(gb.shape).to(gb.dtype)
+        if dw is not None:
+            dw = dw.view(w.shape)
+        return dx, dgb, dw, None, None, None
+
+
+def film_wmean_cat(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, mode="mean",
+                   logits: bool = False) -> torch.Tensor:
+    """``torch.cat((x, film_wmean(x, gb, w, csr, mode, logits)), dim=1)`` without a concatenation pass for the
+    aggregate."""
+    wagg = _wagg(mode)
+    _check_x(x)
+    return FilmWMeanCatFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, wagg)
+
+
+def film_wmean_residual(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, mode="mean",
+                        logits: bool = False) -> torch.Tensor:
+    """``x + film_wmean(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
+    return x + film_wmean(x, gb, w, csr, mode, logits)
+
+
+def film_wmean_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, x0: torch.Tensor,
+                   alpha: float, mode="mean", logits: bool = False) -> torch.Tensor:
+    """``(1 - alpha) * film_wmean(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
+    return (1.0 - float(alpha)) * film_wmean(x, gb, w, csr, mode, logits) + float(alpha) * x0

@@ -15,6 +15,8 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "film_max_bwd_bf16.hip", "film_max_bwd_f16.hip", "film_max_fwd.hip",
                                                     "film_attn_bwd.hip", "film_attn_bwd_bf16.hip", "film_attn_bwd_f16.hip",
                                                     "film_attn_fwd.hip",
+                                                    "film_wmean_bwd.hip", "film_wmean_bwd_bf16.hip",
+                                                    "film_wmean_bwd_f16.hip", "film_wmean_fwd.hip",
                                                     "film_mean_fwd.hip",
                                                     "film_mean_fwd_q_bf16.hip", "film_mean_fwd_q_f16.hip",
                                                     "film_mean_fwd_q.hip",
@@ -31,7 +33,7 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "compress_split_cl.hip", "compress_half_cl.hip")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 HEADERS = [os.path.join(REPO, "include", "mrp_gnn.h")] + [os.path.join(PKG_DIR, "csrc", h) for h in (
-    "film_mean_kernels.hpp", "film_max_kernels.hpp", "film_attn_kernels.hpp", "film_mean_cl_kernels.hpp", "film_mean_bwd_launch.hpp", "film_mean_fwd_launch.hpp", "film_mean_fwd_q_launch.hpp", "fast_math.hpp", "tuning.hpp", "encoder_split.hpp",
+    "film_mean_kernels.hpp", "film_max_kernels.hpp", "film_attn_kernels.hpp", "film_wmean_kernels.hpp", "film_mean_cl_kernels.hpp", "film_mean_bwd_launch.hpp", "film_mean_fwd_launch.hpp", "film_mean_fwd_q_launch.hpp", "fast_math.hpp", "tuning.hpp", "encoder_split.hpp",
     "compress_half_common.hpp", "gemm_common.hpp", "split_common.hpp", "split_nt.hpp")]
 OUT = os.path.join(PKG_DIR, "lib", "libmrp_gnn.so")
 ARCH = os.environ.get("MRP_OFFLOAD_ARCH", "gfx950")

@@ -884,6 +884,49 @@ class FilmCompressFunction(torch.autograd.Function):
         return dx, dgb, dw, db, None, None, None, None
 
 
+class FilmWMeanCompressFunction(torch.autograd.Function):
+    """``conv(torch.cat((x, film_wmean(x, gb, w)), 1))`` with autograd and without the concatenation, as
+    :class:`FilmCompressFunction`: the weighted aggregation into its own buffer, the two-source compress, and
+    in backward ONE aggregation-backward pass that also returns the gradient of the sender maps.  NCHW
+    kernels only: a channels_last x is copied first."""
+
+    @staticmethod
+    def forward(ctx, x, gb, w, weight, bias, csr, flags: int, wagg: int):
+        from .aggregate import film_wmean_forward_into
+        x = x.contiguous()
+        hip = _PATH[0] != "library"
+        agg = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+        film_wmean_forward_into(x, gb, w, csr, flags, agg, wagg)
+        prec = _PRECISION[0]  # read once: both gradients of this node run in the forward's mode
+        y = _fwd(weight, bias, x, agg, cl=False, precision=prec) if hip else _lib_forward(weight, bias, x, agg)
+        ctx.save_for_backward(x, gb, w, agg, weight, bias)
+        ctx.csr, ctx.flags, ctx.wagg, ctx.has_bias, ctx.hip, ctx.precision = csr, flags, wagg, bias is not None, hip, prec
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from .aggregate import film_wmean_backward
+        x, gb, w, agg, weight, bias = ctx.saved_tensors
+        need_x, need_gb, need_w = ctx.needs_input_grad[:3]
+        dx = dgb = dwt = dw = db = None
+        if need_x or need_gb or need_w:
+            gx, ga = _bwd_data(weight, gy, x.dtype, like=x, cl=False, precision=ctx.precision) if ctx.hip else \
+                _lib_backward_data(weight, gy)
+            dx, dgb, dwt = film_wmean_backward(ga, x, gb, w, ctx.csr, ctx.flags, need_x, need_gb, need_w,
+                                               grad_x_base=gx if need_x else None, mode=ctx.wagg)
+            if dgb is not None:
+                dgb = dgb.view(gb.shape).to(gb.dtype)
+            if dwt is not None:
+                dwt = dwt.view(w.shape)
+        if ctx.needs_input_grad[3] or (ctx.has_bias and ctx.needs_input_grad[4]):
+            dw, db = _bwd_weight(gy, x, agg, ctx.has_bias and ctx.needs_input_grad[4], weight, bias,
+                                 want_weight=ctx.needs_input_grad[3], cl=False, precision=ctx.precision) if ctx.hip else \
+                _lib_backward_weight(gy, x, agg, ctx.has_bias)
+            if not ctx.needs_input_grad[3]:
+                dw = None
+        return dx, dgb, dwt, dw, db, None, None, None
+
+
 def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
     """Whether :func:`film_compress` takes this layer: fp32, bf16 or fp16 CUDA (N, C, H, W) features and
     a plain 1x1 ``Conv2d(2C, C)`` with fp32 parameters (the matrix-core kernels, on zero-padded operands
@@ -895,13 +938,30 @@ def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
 
 
 def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int, reducer: str = "mean",
-                  scale=None) -> torch.Tensor:
+                  scale=None, weights=None) -> torch.Tensor:
     """Autograd form of ``conv(torch.cat((x, film_mean(x, gb)), 1))`` without the concatenation
     (:class:`FilmCompressFunction`); the caller checks :func:`film_compress_supported`.  ``reducer="max"``:
     the aggregate is ``film_max(x, gb)`` and ``mode`` carries its flags (0 or ``GB_LOGITS``);
-    ``reducer="attn"``: likewise ``film_attn(x, gb, scale=scale)``."""
-    if reducer not in ("mean", "max", "attn"):
-        raise ValueError(f'reducer must be "mean", "max" or "attn", got {reducer!r}')
+    ``reducer="attn"``: likewise ``film_attn(x, gb, scale=scale)``; ``reducer="wmean"``: the aggregate is
+    ``film_wmean(x, gb, weights)`` with ``mode`` = ``MODE_FILM_MEAN`` or ``MODE_FILM_SUM`` (the normalised or
+    the plain weighted sum), optionally with ``GB_LOGITS`` (:class:`FilmWMeanCompressFunction`)."""
+    if reducer not in ("mean", "max", "attn", "wmean"):
+        raise ValueError(f'reducer must be "mean", "max", "attn" or "wmean", got {reducer!r}')
+    if (weights is not None) != (reducer == "wmean"):
+        raise ValueError('weights belong to reducer="wmean", which needs them')
+    if reducer == "wmean":
+        if scale is not None:
+            raise ValueError('scale belongs to reducer="attn"')
+        base = int(mode) & ~_lib.GB_LOGITS
+        if base not in (_lib.MODE_FILM_MEAN, _lib.MODE_FILM_SUM):
+            raise ValueError(f'reducer="wmean" takes MODE_FILM_MEAN or MODE_FILM_SUM (with or without GB_LOGITS) '
+                             f'as mode, got {int(mode):#x}')
+        if gb is None:
+            raise ValueError("gamma/beta tensor required for film_wmean")
+        gb = gb.reshape(csr.num_edges, x.shape[1], 2)
+        wagg = _lib.WAGG_MEAN if base == _lib.MODE_FILM_MEAN else _lib.WAGG_SUM
+        return FilmWMeanCompressFunction.apply(x, gb, weights, conv.weight, conv.bias, csr,
+                                               int(mode) & _lib.GB_LOGITS, wagg)
     if reducer in ("max", "attn"):
         # `mode` then carries the operator's flags, not a MODE_* value of the mean: say so here, not deep in the launch
         if int(mode) not in (0, _lib.GB_LOGITS):

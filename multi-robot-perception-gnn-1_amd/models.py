@@ -36,6 +36,14 @@ per node (``'node'``); the layer's own-feature terms (cat half, residual, compre
 unquantised features.  In a single-GPU simulation the quantise pass costs more than the aggregation saves:
 the option exists to evaluate and train models for 8-bit links.  The saving belongs to a receiver that is
 handed FP8 buffers (:func:`aggregate.film_mean_q`).  See :meth:`GCN._aggregate_q`.
+
+``opt.gcn_confidence`` (default off: nothing changes, no new parameters): every GCN layer owns a 1x1 head
+``confidence = nn.Conv2d(C, 1, 1)``; each sender attaches ``w = sigmoid(confidence(x))`` to its feature map and
+the receiver averages, pixel by pixel, over what was delivered (:func:`aggregate.film_wmean`; Where2comm-style
+sparse messaging).  ``opt.gcn_confidence_threshold = tau`` hard-gates the map (``w < tau`` is not transmitted:
+0; the gradient flows through the kept values).  Every ``GCN`` method also takes ``weights=`` to supply a map
+(N, H, W) directly.  Modes ``film_mean``, ``film_sum`` and ``copy_mean``; combined with ``film_max``,
+``film_attn`` or ``gcn_message_dtype`` a ``ValueError`` is raised when the module is built.
 """
 from __future__ import annotations
 
@@ -45,6 +53,7 @@ import torch
 import torch.nn as nn
 
 from .aggregate import (film_mean_fq, film_mean_q, film_mean_q_forward_into, quantize_features)
+from .aggregate import film_wmean, film_wmean_cat, film_wmean_mix, film_wmean_residual
 from .aggregate import (film_attn, film_attn_cat, film_attn_mix, film_attn_residual, film_max, film_max_cat,
                         film_max_mix, film_max_residual, film_mean, film_mean_cat, film_mean_mix, film_mean_residual)
 from .compress import CompressFunction, compress_1x1, compress_path, film_compress, film_compress_supported
@@ -131,6 +140,27 @@ def message_format(opt):
     return MESSAGE_DTYPES[dtype], per
 
 
+def confidence_options(opt):
+    """(head?, threshold or None) from ``opt.gcn_confidence`` / ``opt.gcn_confidence_threshold``; a combination
+    the weighted aggregation does not provide is a ``ValueError`` (raised when a module is built)."""
+    on = bool(_opt(opt, "gcn_confidence", False))
+    tau = _opt(opt, "gcn_confidence_threshold", None)
+    if on:
+        _check_weighted(opt)
+    if tau is not None and not 0.0 <= float(tau) <= 1.0:
+        raise ValueError(f"gcn_confidence_threshold must be in [0, 1], got {tau!r}")
+    return on, (None if tau is None else float(tau))
+
+
+def _check_weighted(opt) -> None:
+    mode = _opt(opt, "gcn_mode", "film_mean")
+    if mode in ("film_max", "film_attn"):
+        raise ValueError(f"confidence-weighted aggregation is not provided for gcn_mode={mode!r} "
+                         "(film_mean, film_sum, copy_mean)")
+    if _opt(opt, "gcn_message_dtype", None) is not None:
+        raise ValueError("confidence-weighted aggregation is not provided together with gcn_message_dtype")
+
+
 #: ``gcn_return`` given to a GCN unpickled from a reference checkpoint whose ``opt`` has none (see
 #: :meth:`GCN.__setstate__`); ``compat.reference_class_path(gcn_return=...)`` sets it.
 UNPICKLED_GCN_RETURN = "input"
@@ -144,6 +174,8 @@ class GCN(_PackedImages, nn.Module):
         self.opt = opt
         message_format(opt)  # an unknown gcn_message_dtype / gcn_message_scale: ValueError here
         self.edge_encoder = edge_encoder(layers_dim=[opt.feature_dim, opt.feature_dim])
+        if confidence_options(opt)[0]:  # a forbidden combination: ValueError here
+            self.confidence = nn.Conv2d(opt.feature_dim, 1, kernel_size=1)
         # marks a GCN this framework built: its pickles (deepcopy, torch.save of the whole model as the
         # reference's training.py:345-355 does) keep computing the aggregate
         self.gcn_return_default = "aggregate"
@@ -170,6 +202,35 @@ class GCN(_PackedImages, nn.Module):
         """``opt.gcn_attn_scale``: the score scale of ``gcn_mode='film_attn'`` (None: 1/sqrt(C))."""
         return _opt(self.opt, "gcn_attn_scale", None)
 
+    def confidence_map(self, x: torch.Tensor) -> torch.Tensor:
+        """The sender maps w (N, 1, H, W) fp32 of feature maps x: ``sigmoid(confidence(x))``, hard-gated by
+        ``opt.gcn_confidence_threshold`` (values below it become 0; the kept ones carry the gradient)."""
+        if "confidence" not in self._modules:
+            raise ValueError("GCN.confidence_map needs opt.gcn_confidence (the module has no confidence head)")
+        w = torch.sigmoid(self.confidence(x.to(self.confidence.weight.dtype))).float()
+        tau = confidence_options(self.opt)[1]
+        if tau is not None:
+            w = torch.where(w >= tau, w, torch.zeros_like(w))
+        return w.contiguous()
+
+    def _weights(self, x, weights):
+        """The sender maps of this call: ``weights=`` if given, else the head's, else None (unweighted)."""
+        if weights is not None:
+            _check_weighted(self.opt)
+            return weights
+        return self.confidence_map(x) if "confidence" in self._modules else None
+
+    def _wmean_args(self, g, x):
+        """(gb or logits, csr, mode, logits?) of the weighted aggregation for ``opt.gcn_mode``; ``copy_mean`` is
+        gamma = 1, beta = 0, materialised."""
+        mode = _opt(self.opt, "gcn_mode", "film_mean")
+        csr = g.csr(x.device)
+        if mode == "copy_mean":
+            gb = torch.zeros((csr.num_edges, x.shape[1], 2), device=x.device, dtype=torch.float32)
+            gb[:, :, 0] = 1.0
+            return gb, csr, "mean", False
+        return self.edge_encoder.logits(g.edata["pose"]), csr, ("sum" if mode == "film_sum" else "mean"), True
+
     def _aggregate_q(self, g, x, fmt, per, x0=None, agg_scale=1.0, x0_scale=0.0, out=None):
         """``agg_scale * aggregate(quantised x) + x0_scale * x0`` for ``opt.gcn_message_dtype``, in x's
         dtype.  Grad mode off and CUDA features: ``quantize_features`` + the native FP8 kernel
@@ -194,15 +255,20 @@ class GCN(_PackedImages, nn.Module):
         a = film_mean_fq(x, z, csr, fmt, per, mode, logits=True, x0=x0, agg_scale=agg_scale, x0_scale=x0_scale)
         return a if out is None else out.copy_(a)
 
-    def forward(self, g, feats: torch.Tensor = None) -> torch.Tensor:
+    def forward(self, g, feats: torch.Tensor = None, weights: torch.Tensor = None) -> torch.Tensor:
         """The aggregate of ``feats`` (fp32, bf16 or fp16; returned in that dtype — the encoder's logits
-        stay fp32 and the aggregation's arithmetic is fp32 either way)."""
+        stay fp32 and the aggregation's arithmetic is fp32 either way).  ``weights`` (N, H, W) fp32, or the
+        module's confidence head: the confidence-weighted aggregate (module docstring)."""
         x = g.ndata["image"] if feats is None else feats
+        w = self._weights(x, weights)
         fmt, per = message_format(self.opt)
         if fmt is not None:
             return self._aggregate_q(g, x, fmt, per)
         if self._return_mode() == "input":
             return x  # models.py:226 returns the input; update_all's result is never read
+        if w is not None:
+            gb, csr, wmode, logits = self._wmean_args(g, x)
+            return film_wmean(x, gb, w, csr, wmode, logits=logits)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
         if mode == "copy_mean":
             return film_mean(x, None, g.csr(x.device), mode)
@@ -214,10 +280,11 @@ class GCN(_PackedImages, nn.Module):
             return film_attn(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean(x, z, g.csr(x.device), mode, logits=True)
 
-    def forward_cat(self, g, feats: torch.Tensor = None) -> torch.Tensor:
+    def forward_cat(self, g, feats: torch.Tensor = None, weights: torch.Tensor = None) -> torch.Tensor:
         """``torch.cat((feats, self(g, feats)), 1)`` (``models.py:181-182``) with the aggregate written
         straight into the concatenation buffer (and the backward fused likewise)."""
         x = g.ndata["image"] if feats is None else feats
+        w = self._weights(x, weights)  # explicit maps with an unsupported option: ValueError here
         fmt, per = message_format(self.opt)
         if fmt is not None:
             if torch.is_grad_enabled() or not x.is_cuda:
@@ -227,6 +294,9 @@ class GCN(_PackedImages, nn.Module):
             self._aggregate_q(g, x, fmt, per, out=cat[:, C:])
             cat[:, :C].copy_(x)
             return cat
+        if w is not None and self._return_mode() != "input":
+            gb, csr, wmode, logits = self._wmean_args(g, x)
+            return film_wmean_cat(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
             return torch.cat((x, self(g, x)), dim=1)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -240,7 +310,8 @@ class GCN(_PackedImages, nn.Module):
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
 
-    def forward_cat_compress(self, g, feats: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
+    def forward_cat_compress(self, g, feats: torch.Tensor, conv: nn.Conv2d,
+                             weights: torch.Tensor = None) -> torch.Tensor:
         """``conv(torch.cat((feats, self(g, feats)), 1))`` (``models.py:181-184``) without the
         concatenation: the aggregation kernel into its own buffer, then the matrix-core compress
         reading x and the aggregate in place, and in backward the data-gradient kernel writing x's
@@ -258,6 +329,7 @@ class GCN(_PackedImages, nn.Module):
         features do the same after ``compress.set_channels_last_compress_fp32('native')``
         (``compress_split_cl.hip``; by default they are copied to NCHW and the layer returns NCHW)."""
         x = feats
+        w = self._weights(x, weights)  # explicit maps with an unsupported option: ValueError here
         fmt, per = message_format(self.opt)
         if fmt is not None:
             # the aggregate of the quantised messages into its own buffer, then the compress kernels on
@@ -266,6 +338,12 @@ class GCN(_PackedImages, nn.Module):
             if x.is_cuda and film_compress_supported(conv, x):
                 return CompressFunction.apply(x, a, conv.weight, conv.bias)
             return compress_1x1(conv, torch.cat((x, a), dim=1))
+        if w is not None and self._return_mode() != "input":
+            if x.is_cuda and compress_path() != "library" and film_compress_supported(conv, x):
+                gb, csr, wmode, logits = self._wmean_args(g, x)
+                flags = _lib_modes()["film_sum" if wmode == "sum" else "film_mean"] | (_lib_logits() if logits else 0)
+                return film_compress(conv, x, gb, csr, flags, reducer="wmean", weights=w)
+            return compress_1x1(conv, self.forward_cat(g, x, weights=w))
         if (x.is_cuda and self._return_mode() != "input" and compress_path() != "library"
                 and film_compress_supported(conv, x)):
             mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -280,13 +358,17 @@ class GCN(_PackedImages, nn.Module):
             return film_compress(conv, x, z, g.csr(x.device), _lib_modes()[mode] | _lib_logits())
         return compress_1x1(conv, self.forward_cat(g, x))
 
-    def forward_residual(self, g, feats: torch.Tensor = None) -> torch.Tensor:
+    def forward_residual(self, g, feats: torch.Tensor = None, weights: torch.Tensor = None) -> torch.Tensor:
         """``feats + self(g, feats)`` in one kernel pass: the residual combination ``h = g_h + h``
         of ``dgl/model/dgl_models.py:36-37`` (the FiLM-mean 'add' variant)."""
         x = g.ndata["image"] if feats is None else feats
+        w = self._weights(x, weights)  # explicit maps with an unsupported option: ValueError here
         fmt, per = message_format(self.opt)
         if fmt is not None:  # the layer's own h through the epilogue's x0, unquantised
             return self._aggregate_q(g, x, fmt, per, x0=x, x0_scale=1.0)
+        if w is not None and self._return_mode() != "input":
+            gb, csr, wmode, logits = self._wmean_args(g, x)
+            return film_wmean_residual(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
             return x + self(g, x)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -299,13 +381,18 @@ class GCN(_PackedImages, nn.Module):
             return film_attn_residual(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean_residual(x, z, g.csr(x.device), mode, logits=True)
 
-    def forward_mix(self, g, feats: torch.Tensor, x0: torch.Tensor, alpha: float) -> torch.Tensor:
+    def forward_mix(self, g, feats: torch.Tensor, x0: torch.Tensor, alpha: float,
+                    weights: torch.Tensor = None) -> torch.Tensor:
         """``(1 - alpha) * self(g, feats) + alpha * x0`` in one kernel pass: a GCN2-style
         initial-feature mix (BASELINE configs[3]'s "GCN2Conv"; not in the reference)."""
         x = feats
+        w = self._weights(x, weights)  # explicit maps with an unsupported option: ValueError here
         fmt, per = message_format(self.opt)
         if fmt is not None:
             return self._aggregate_q(g, x, fmt, per, x0=x0, agg_scale=1.0 - float(alpha), x0_scale=float(alpha))
+        if w is not None and self._return_mode() != "input":
+            gb, csr, wmode, logits = self._wmean_args(g, x)
+            return film_wmean_mix(x, gb, w, csr, x0, alpha, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
             return (1.0 - alpha) * self(g, x) + alpha * x0
         mode = _opt(self.opt, "gcn_mode", "film_mean")

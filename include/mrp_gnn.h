@@ -663,6 +663,110 @@ int64_t mrp_film_wmean_workspace(int32_t num_graphs, int32_t max_nodes, int32_t 
                                  int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
 
 /*
+ * The confidence-gated attention fusion (ABI 22, extended): mrp_film_attn_* over what was delivered.  Every
+ * sender u attaches a per-pixel map w[u,p] >= 0 (mrp_film_wmean_*'s: (num_nodes, P) fp32, node stride
+ * w_node_stride >= P, indexed by SOURCE node); at each pixel the receiver attends over the senders that
+ * delivered something there, each weighted by its confidence.  An operator of its own: the attention kernels
+ * compiled with the gate (a lane owns a pixel, so w is lane-private and enters the softmax step only); every
+ * other entry point is unchanged.  Everything not restated here is exactly mrp_film_attn_*: row order, every
+ * graph kind, parallel edges, self-loops, in-degree <= MRP_FILM_ATTN_DEGREE, MRP_AGG_GB_LOGITS, scale, node
+ * strides, 16-bit widening.
+ *
+ * For destination v, entries j of its CSR row in row order, e_j the edge, u_j the source, w_j[p] = w[u_j,p].
+ * Entry j is DELIVERED at p iff w_j[p] > 0; a zero, negative or NaN weight compares false: a silent entry.
+ *
+ *   m_j[c,p], s_j[p]     as mrp_film_attn_fwd, bit for bit (same chains, same order)
+ *   mx[p]   = max over delivered j of s_j[p]
+ *   u_j[p]  = exp(s_j[p] - mx[p])             v_exp_f32 on the difference, for every entry of the row
+ *   t_j[p]  = fl(w_j[p] * u_j[p])             delivered entries
+ *   Z[p]    = sum of t_j over delivered j     row order, one chain
+ *   a_j[p]  = fl(t_j / Z)   delivered j and Z > 0 (IEEE division); 0 for a silent j, Z == 0, an empty row
+ *   r_j[p]  = fl(u_j / Z)   EVERY entry where Z > 0 (IEEE division);  0 where nobody delivered
+ *   out[v,c,p]  = sum over delivered j, row order, of a_j * m_j: the bare product at the first delivered entry,
+ *                 an fma chain after it (film_attn's chain, started there); an exact 0 where nobody delivered
+ *   attn[e_j,p] = a_j[p]    (E, P) fp32, an output
+ *   rate[e_j,p] = r_j[p]    (E, P) fp32, an output; may be NULL (inference): only grad_w needs it
+ *
+ * Silent entries are skipped by per-lane selects, never multiplied by zero: a silent sender's features, however
+ * non-finite, reach out, attn, grad_x and grad_gb nowhere — only that sender's own rate and grad_w at that
+ * pixel (and, as for film_attn, whatever that node receives itself: its features are its own row's query).
+ * mx is taken over the delivered entries only, so a silent entry that outscores every delivered one by more
+ * than the fp32 exponent range has rate = +inf, and grad_w follows IEEE from there; nothing is clamped.
+ *
+ * Backward, g = grad_out[v].  It reads attn and rate as the forward wrote them and recomputes the messages,
+ * not the softmax:
+ *
+ *   da_j[p]  = sum_c g[c,p] * m_j[c,p]                   every entry, channels ascending
+ *   dbar[p]  = sum over delivered k, row order, of a_k * da_k     (an fma chain from 0)
+ *   ds_j[p]  = a_j * (da_j - dbar)                       0 for a silent j
+ *   dm_j, grad_x (query, key and value paths, + grad_x_base), grad_gb: mrp_film_attn_bwd's formulas with these
+ *            a and ds; silent entries contribute nothing (their grad_gb rows are zeros)
+ *   grad_w[u,p] = sum over all (v, j) with u_j = u of r_j[p] * (da_j[p] - dbar[p])     an fma chain from 0,
+ *            destinations ascending, then row order
+ *
+ * grad_w is the exact one-sided derivative: it includes the entries with w_j = 0, where it is in general not
+ * zero (as mrp_film_wmean_bwd's), and is 0 where Z = 0.  grad_w (num_nodes, P) fp32 with node stride
+ * gw_node_stride >= P; every node's row is written (zeros for a node nobody hears).  A workgroup owns all of a
+ * graph's nodes at its 64 pixels, so the sum never crosses a workgroup: the waves take turns in destination
+ * order on one LDS cell per (node, pixel).  No atomics, one writer per element.
+ *
+ * Consequences, bit for bit on finite operands:
+ *   - w == 1 gives mrp_film_attn_fwd's out and attn (rate == attn) and mrp_film_attn_bwd's grad_x and grad_gb;
+ *   - a 0/1 map constant over each node's plane gives mrp_film_attn_*'s out, attn, grad_x and grad_gb on the
+ *     graph without the silent robots' out-edges (same E and edge ids, rows compacted); the removed edges'
+ *     rows are zeros on both sides;
+ *   - 16-bit features: fwd(T, x) == T(fwd(float(x))); attn, rate, grad_gb and grad_w are equal in fp32, and
+ *     grad_x == T(fp32 grad_x) on widened operands.
+ *
+ * Determinism and the order of every other sum: mrp_film_attn_*'s.  Preconditions: those of mrp_film_attn_*,
+ * and w < +inf.
+ *
+ * grad_x, grad_gb and grad_w may each be NULL to skip that output; all NULL returns success without a launch
+ * (grad_w alone skips the second channel sweep).  Validation precedes any launch and is mrp_film_attn_*'s; in
+ * addition hipErrorInvalidValue is returned for a NULL w with work to do, w_node_stride < P, gw_node_stride < P
+ * with grad_w wanted, a non-NULL grad_w with a NULL rate (where there are edges), and a workspace smaller than
+ * needed.  Empty work returns success (attn, rate, grad_gb and grad_w, where given, are zeros).  No
+ * allocation, no host synchronisation, capturable (hipMemsetAsync of attn, rate / grad_gb precedes the kernels
+ * of non-COMPLETE graphs: rows no CSR entry names are zeros).
+ *
+ * mrp_film_wattn_workspace(direction, ...) is mrp_film_attn_workspace's value: 0 for the forward; for the
+ * backward the per-tile grad_gb partials where a plane spans several 64-pixel tiles (needed only where grad_gb
+ * is wanted; grad_w needs none).  It makes no GPU call.
+ */
+int mrp_film_wattn_fwd(int32_t dtype,
+                       const void* x, int64_t x_node_stride,
+                       const float* gb,
+                       const float* w, int64_t w_node_stride,
+                       const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                       const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                       int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                       int32_t C, int32_t P, int32_t flags,
+                       void* out, int64_t out_node_stride,
+                       float scale, float* attn, float* rate,
+                       void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+int mrp_film_wattn_bwd(int32_t dtype,
+                       const void* grad_out, int64_t g_node_stride,
+                       const void* x, int64_t x_node_stride,
+                       const float* gb,
+                       const float* w, int64_t w_node_stride,
+                       const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                       const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                       int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                       int32_t C, int32_t P, int32_t flags,
+                       void* grad_x, int64_t gx_node_stride,
+                       const void* grad_x_base, int64_t base_node_stride,
+                       float* grad_gb,
+                       float scale, const float* attn, const float* rate,
+                       float* grad_w, int64_t gw_node_stride,
+                       void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+int64_t mrp_film_wattn_workspace(int32_t direction, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                 int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

@@ -18,6 +18,8 @@ from .aggregate import (FilmWMeanCatFunction, FilmWMeanFunction, film_wmean, fil
                         film_wmean_cat, film_wmean_forward_into, film_wmean_mix, film_wmean_residual)
 from .aggregate import (FilmAttnCatFunction, FilmAttnFunction, film_attn, film_attn_backward,  # noqa: F401
                         film_attn_cat, film_attn_forward_into, film_attn_mix, film_attn_residual)
+from .aggregate import (FilmWAttnCatFunction, FilmWAttnFunction, film_wattn, film_wattn_backward,  # noqa: F401
+                        film_wattn_cat, film_wattn_forward_into, film_wattn_mix, film_wattn_residual)
 from . import compat, compress, encoder  # noqa: F401
 from .compress import compress_precision, compress_precision_scope, set_compress_precision  # noqa: F401
 from .compress import channels_last_compress_fp32, set_channels_last_compress_fp32  # noqa: F401

@@ -39,6 +39,9 @@ EXPORTED_SYMBOLS = (
     "mrp_film_attn_fwd",
     "mrp_film_attn_bwd",
     "mrp_film_attn_workspace",
+    "mrp_film_wattn_fwd",
+    "mrp_film_wattn_bwd",
+    "mrp_film_wattn_workspace",
     "mrp_film_wmean_fwd",
     "mrp_film_wmean_bwd",
     "mrp_film_wmean_workspace",
@@ -218,6 +221,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_attn_bwd.restype = ctypes.c_int
     lib.mrp_film_attn_workspace.argtypes = [_I32] * 8
     lib.mrp_film_attn_workspace.restype = ctypes.c_int64
+    # the confidence-gated attention fusion: film_attn's lists with (w, w_node_stride) after gb; the forward adds
+    # rate after attn, the backward rate, grad_w, gw_node_stride
+    fa, ba = lib.mrp_film_attn_fwd.argtypes, lib.mrp_film_attn_bwd.argtypes
+    lib.mrp_film_wattn_fwd.argtypes = fa[:4] + [_P, _I64] + fa[4:-3] + [_P] + fa[-3:]
+    lib.mrp_film_wattn_fwd.restype = ctypes.c_int
+    lib.mrp_film_wattn_bwd.argtypes = ba[:6] + [_P, _I64] + ba[6:-3] + [_P, _P, _I64] + ba[-3:]
+    lib.mrp_film_wattn_bwd.restype = ctypes.c_int
+    lib.mrp_film_wattn_workspace.argtypes = [_I32] * 8
+    lib.mrp_film_wattn_workspace.restype = ctypes.c_int64
     # the confidence-weighted aggregation: (w, w_node_stride) follow gb, wagg follows flags; the backward
     # ends with grad_w, gw_node_stride, workspace, workspace_bytes, stream
     lib.mrp_film_wmean_fwd.argtypes = [_I32, _P, _I64, _P, _P, _I64] + graph[:-1] + [_I32, _I32, _P, _I64, _P]

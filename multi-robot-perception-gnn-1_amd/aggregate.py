@@ -1410,3 +1410,223 @@ def film_wmean_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: Grap
                    alpha: float, mode="mean", logits: bool = False) -> torch.Tensor:
     """``(1 - alpha) * film_wmean(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
     return (1.0 - float(alpha)) * film_wmean(x, gb, w, csr, mode, logits) + float(alpha) * x0
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Confidence-gated attention fusion (``mrp_film_wattn_fwd`` / ``_bwd``): ``film_attn`` over what was delivered.
+#
+#     m_j, s_j  as film_attn                                     for v's in-edges e_j, u_j = src(e_j)
+#     a_j   = w[u_j] exp(s_j - mx) / sum_k w[u_k] exp(s_k - mx)  per pixel, over the entries with w[u_j] > 0
+#     out_v = sum_j a_j * m_j                                    0 where nobody delivered
+#
+# ``w`` (N, H, W) fp32 >= 0 is ``film_wmean``'s sender map; an entry with w == 0 at a pixel is silent there: it
+# takes no part in the softmax and its features reach nothing.  Gradients for x, gb and w; ``attn`` (E, H*W)
+# is an output as for ``film_attn``, and ``rate`` (E, H*W), the softmax's response to each sender's weight, is
+# computed only when w needs a gradient.  With w == 1 it gives ``film_attn``'s bits.  channels_last features
+# take the copy-first route.
+# ---------------------------------------------------------------------------------------------------------
+def film_wattn_forward_into(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, flags: int,
+                            out: torch.Tensor, scale: Optional[float] = None, attn: Optional[torch.Tensor] = None,
+                            rate=False):
+    """Run ``mrp_film_wattn_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
+    half of a ``torch.cat((h, g_h), 1)`` buffer — and return ``(attn, rate)``: the weights (E, H*W) fp32
+    (written into the given tensor, else a new one) and, with ``rate=True`` or a tensor to write into, the
+    rates (E, H*W) fp32 the backward needs for grad_w (else None).  ``flags``: 0 or ``_lib.GB_LOGITS``.  No
+    autograd."""
+    _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _require_device(x, out, attn, rate if isinstance(rate, torch.Tensor) else None)
+    flags = _check_attn_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    scale = _attn_scale(scale, C)
+    x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
+    os_ = node_stride(out)
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    w, wst = _wmean_weights(w, n, H, W)
+    gb = _attn_gb(gb, csr, C)
+    bufs = []
+    for name, t in (("attn", attn), ("rate", rate)):
+        if t is None or t is False:
+            t = None if name == "rate" else torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
+        elif t is True:
+            t = torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
+        elif tuple(t.shape) != (csr.num_edges, H * W) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {(csr.num_edges, H * W)} float32 tensor")
+        bufs.append(t)
+    attn, rate = bufs
+    lib = _lib.load_library()
+    ga = _graph_args(gb, csr, C, H * W, flags)
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_wattn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, ga[0], _ptr(w), wst, *ga[1:], _ptr(out),
+                                      os_, scale, _ptr(attn), _ptr(rate), None, 0, _stream(x.device))
+    _lib.check(code, "mrp_film_wattn_fwd")
+    PATH_COUNTS["wattn_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+    return attn, rate
+
+
+def film_wattn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor,
+                        attn: torch.Tensor, rate: Optional[torch.Tensor], csr: GraphCSR, flags: int, need_dx: bool,
+                        need_dgb: bool, need_dw: bool, grad_x_base: Optional[torch.Tensor] = None,
+                        scale: Optional[float] = None):
+    """(grad_x, grad_gb (E, C, 2), grad_w (N, H, W)) of :func:`film_wattn_forward_into`, each None unless asked
+    for; ``attn`` and ``rate`` are what it returned (``rate`` is needed for grad_w only); ``grad_x_base``
+    (N, C, H, W), if given, is added into grad_x by the kernel.  grad_x is NCHW in x's dtype, grad_gb and grad_w
+    are fp32."""
+    _check_attn_degree(csr)
+    _require_device(grad_out, x, attn, rate)
+    flags = _check_attn_flags(flags)
+    if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
+    n, C, H, W = x.shape
+    scale = _attn_scale(scale, C)
+    if n != csr.num_nodes:
+        raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
+    # the kernel reads grad_out, the base, attn and rate with x's extents: a mismatch would be an out-of-bounds read
+    if tuple(grad_out.shape) != (n, C, H, W):
+        raise ValueError(f"grad_out must be {(n, C, H, W)}, got {tuple(grad_out.shape)}")
+    if grad_x_base is not None and tuple(grad_x_base.shape) != (n, C, H, W):
+        raise ValueError(f"grad_x_base must be {(n, C, H, W)}, got {tuple(grad_x_base.shape)}")
+    for name, t in (("attn", attn), ("rate", rate)):
+        if t is None and name == "rate":
+            if need_dw:
+                raise ValueError("grad_w needs the forward's rate (film_wattn_forward_into(..., rate=True))")
+            continue
+        if tuple(t.shape) != (csr.num_edges, H * W) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be {(csr.num_edges, H * W)} float32, got {tuple(t.shape)} {t.dtype}")
+    if grad_x_base is not None:
+        _require_device(grad_x_base)
+    w, wst = _wmean_weights(w, n, H, W)
+    if not (need_dx or need_dgb or need_dw):
+        return None, None, None
+    attn = attn.contiguous()
+    rate = rate.contiguous() if rate is not None and need_dw else None
+    dtype = x.dtype
+    if grad_out.dtype != dtype:
+        grad_out = grad_out.to(dtype)
+    grad_out, gs = _as_node_major(grad_out)
+    x, xs = _as_node_major(x)
+    bs = 0
+    if grad_x_base is not None and need_dx:
+        if grad_x_base.dtype != dtype:
+            grad_x_base = grad_x_base.to(dtype)
+        grad_x_base, bs = _as_node_major(grad_x_base)
+    else:
+        grad_x_base = None
+    dx = torch.empty((n, C, H, W), device=x.device, dtype=dtype) if need_dx else None
+    dgb = torch.empty((csr.num_edges, C, 2), device=x.device, dtype=torch.float32) if need_dgb else None
+    dw = torch.empty((n, H, W), device=x.device, dtype=torch.float32) if need_dw else None
+    gb = _attn_gb(gb, csr, C)
+    ga = _graph_args(gb, csr, C, H * W, flags)
+    lib = _lib.load_library()
+    work, nbytes = None, 0
+    if need_dgb:
+        nbytes = lib.mrp_film_wattn_workspace(1, csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes,
+                                              csr.num_edges, C, H * W)
+        if nbytes > 0:
+            work = torch.empty(((nbytes + 3) // 4,), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        code = lib.mrp_film_wattn_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, ga[0], _ptr(w), wst,
+                                      *ga[1:], _ptr(dx), (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs,
+                                      _ptr(dgb), scale, _ptr(attn), _ptr(rate), _ptr(dw),
+                                      H * W if dw is not None else 0, _ptr(work), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_wattn_bwd")
+    PATH_COUNTS["wattn_bwd_" + _DTYPE_KEYS[dtype]] += 1
+    return dx, dgb, dw
+
+
+def _wattn_grads(ctx, grad_out, base):
+    x, gb, w, attn, rate = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    dx, dgb, dw = film_wattn_backward(grad_out, x, gb, w, attn, rate, ctx.csr, ctx.flags, need[0], need[1], need[2],
+                                      grad_x_base=base if need[0] else None, scale=ctx.scale)
+    if dgb is not None:
+        dgb = dgb.view(gb.shape).to(gb.dtype)
+    if dw is not None:
+        dw = dw.view(w.shape)
+    return dx, dgb, dw, None, None, None
+
+
+class FilmWAttnFunction(torch.autograd.Function):
+    """Autograd wrapper: forward = ``mrp_film_wattn_fwd``, backward = ``mrp_film_wattn_bwd`` with gradients for
+    x, gb and w.  Returns (out, attn); attn is saved for the backward and is not differentiable; the rates are
+    computed and saved only when w requires a gradient.  ``flags`` may be ``_lib.GB_LOGITS``."""
+
+    @staticmethod
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale):
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, out, scale, rate=ctx.needs_input_grad[2])
+        ctx.save_for_backward(x, gb, w, attn, rate)
+        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_attn):
+        return _wattn_grads(ctx, grad_out, None)
+
+
+def film_wattn(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
+               scale: Optional[float] = None, return_weights: bool = False):
+    """:func:`film_attn` over what was delivered: at every pixel the receiver attends over the in-neighbours
+    whose map ``w`` is positive there, each softmax term weighted by the sender's confidence
+    (``a_j ~ w[src e_j] exp(s_j)``); pixels nobody delivered to give 0, and a silent sender's features reach
+    nothing.  Differentiable in x, gb and w (w's gradient includes the entries at w == 0: the one-sided
+    derivative).
+
+    x: (N, C, H, W) fp32, bf16 or fp16 on a ROCm device; gb: (E, 2C) or (E, C, 2) interleaved gamma/beta, or
+    their pre-sigmoid logits with ``logits=True``; w: (N, H, W) or (N, 1, H, W) fp32 >= 0, each node's plane
+    contiguous — the sender's map, indexed by source node; csr: ``RobotGraph.csr(device)``, every in-degree <=
+    ``_lib.FILM_ATTN_DEGREE``.  With ``return_weights=True`` returns ``(out, attn)``, attn (E, H*W) fp32 by edge
+    id, not differentiable."""
+    _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _check_x(x)
+    out, attn = FilmWAttnFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale)
+    return (out, attn) if return_weights else out
+
+
+class FilmWAttnCatFunction(torch.autograd.Function):
+    """``torch.cat((x, film_wattn(x, gb, w)), 1)``: the kernel writes the aggregate into the second half of the
+    (N, 2C, H, W) buffer through its node stride, x is copied into the first half by torch; backward hands
+    the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
+
+    @staticmethod
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale):
+        n, C, H, W = x.shape
+        buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, buf[:, C:], scale, rate=ctx.needs_input_grad[2])
+        buf[:, :C].copy_(x)
+        ctx.save_for_backward(x, gb, w, attn, rate)
+        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.mark_non_differentiable(attn)
+        return buf, attn
+
+    @staticmethod
+    def backward(ctx, grad_buf, _grad_attn):
+        C = ctx.saved_tensors[0].shape[1]
+        return _wattn_grads(ctx, grad_buf[:, C:], grad_buf[:, :C])
+
+
+def film_wattn_cat(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
+                   scale: Optional[float] = None, return_weights: bool = False):
+    """``torch.cat((x, film_wattn(x, gb, w, csr, logits, scale)), dim=1)`` without a concatenation pass for the
+    aggregate."""
+    _check_attn_degree(csr)
+    _check_x(x)
+    buf, attn = FilmWAttnCatFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale)
+    return (buf, attn) if return_weights else buf
+
+
+def film_wattn_residual(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
+                        scale: Optional[float] = None) -> torch.Tensor:
+    """``x + film_wattn(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
+    return x + film_wattn(x, gb, w, csr, logits, scale)
+
+
+def film_wattn_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, x0: torch.Tensor, alpha: float,
+                   logits: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+    """``(1 - alpha) * film_wattn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
+    return (1.0 - float(alpha)) * film_wattn(x, gb, w, csr, logits, scale) + float(alpha) * x0

@@ -45,6 +45,10 @@ namespace mrp_host {
 hipError_t launch_attn_bwd_f32(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st) {
   return launch_attn_bwd<float>(m, ck, ks, lds, grid, st);
 }
+hipError_t launch_attn_dgb_reduce(const AttnArgs& m, int64_t blocks, hipStream_t st) {
+  hipLaunchKernelGGL(mrp::film_attn_dgb_reduce, dim3((unsigned)blocks), dim3(mrp::kBlock), 0, st, m);
+  return hipGetLastError();
+}
 }  // namespace mrp_host
 
 extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x,

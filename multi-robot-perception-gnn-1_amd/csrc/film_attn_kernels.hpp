@@ -32,6 +32,19 @@
 // summed in wave order; d gamma / d beta of a slot are reduced over the tile's 64 pixels by a fixed butterfly
 // and, where a plane spans several tiles, written per tile to a workspace that film_attn_dgb_reduce sums in
 // tile order.  No atomics anywhere.
+//
+// WGT = true instantiates the same kernels as the confidence-gated fusion (mrp_film_wattn_fwd / _bwd,
+// film_wattn_*.hip): a sender map w[u, p] gates and weights the softmax.  A lane owns a pixel, so w is lane-private
+// data: the graph's n x 64 weights are staged in LDS once per workgroup next to the row tables, "entry j delivered
+// at this pixel" (w > 0) is a per-lane bit, and every place that discards a slot past the row's end with a
+// wave-uniform select discards a silent entry with a per-lane one instead — a silent entry is never multiplied
+// by zero.  The channel sweeps are unchanged (the silent slots' scores are formed and kept: grad_w needs their
+// da_j); only the softmax step, the ds step and the selects differ.  grad_w[u, p] sums over the destinations in
+// ascending order: the waves take turns, one destination at a time, on one lane-private LDS cell per (node,
+// pixel) — at most 16 barriers per workgroup, one writer per element, no atomics.  WGT = false compiles the
+// statements film_attn always had.
+
+#include <type_traits>
 
 #include "film_mean_kernels.hpp"
 
@@ -56,6 +69,17 @@ struct AttnArgs {
   int64_t E;
 };
 
+// The WGT kernels' argument block (film_attn's own kernels keep AttnArgs as it was).
+struct WAttnArgs : AttnArgs {
+  const float* w;    // (nodes, P) sender maps by source node, node stride wst
+  int64_t wst;
+  float* rate;       // (E, P) d a_j / d w_j up to the centring, by edge id (fwd: written if non-null, bwd: read)
+  float* gw;         // backward: grad_w (nodes, P), node stride gwst; null: not wanted
+  int64_t gwst;
+};
+template <bool WGT>
+using AttnArgsOf = std::conditional_t<WGT, WAttnArgs, AttnArgs>;
+
 // LDS of one workgroup for graphs of up to nmax nodes and chunks of ck channels.
 struct AttnLds {
   float* X;                    // [ck][nmax][64] the chunk's x, widened
@@ -64,7 +88,7 @@ struct AttnLds {
   float* D;                    // backward: [4 waves][ck][nmax][64] grad_x partials
   unsigned long long* slot_u;  // [nmax] the row's local sources, 4 bits each, slot 0 lowest
   int* slot_e;                 // [nmax * 16] edge id, -1: no such slot
-  int* rowlen;                 // [nmax]
+  int* rowlen;                 // [nmax]; WGT: followed by [nmax][64] the tile's sender weights (attn_wt)
   __device__ __forceinline__ AttnLds(void* smem, int nmax, int ck, bool bwd) {
     X = reinterpret_cast<float*>(smem);
     W = reinterpret_cast<float2*>(X + ck * nmax * kAttnTile);
@@ -75,6 +99,19 @@ struct AttnLds {
     rowlen = slot_e + nmax * kAttnSlots;
   }
 };
+
+__device__ __forceinline__ float* attn_wt(const AttnLds& L, int nmax) {
+  return reinterpret_cast<float*>(L.rowlen + nmax);
+}
+
+// WGT: the tile's weights of the graph's nodes into LDS (zeros past the plane's end: silent).  Wave w stages the
+// nodes it stages x of.  Published by the barrier that ends attn_tables.
+__device__ __forceinline__ void attn_stage_w(const WAttnArgs& m, const AttnLds& L, int node0, int n, int p, bool pin) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* Wt = attn_wt(L, m.a.nmax);
+  for (int u = wave; u < n; u += kAttnWaves)
+    Wt[u * kAttnTile + lane] = pin ? m.w[(int64_t)(node0 + u) * m.wst + p] : 0.f;
+}
 
 // Row lengths, sources and edge ids of the graph's rows (film_max's tables).  Ends with a barrier.
 __device__ __forceinline__ void attn_tables(const AttnArgs& m, const AttnLds& L, int b, int node0, int n) {
@@ -265,8 +302,8 @@ __device__ __forceinline__ float wave_sum63(float x) {
 // Forward.  Workgroup = graph x pixel tile.  KS: compiled slots per destination (4, 8 or 16; the launcher picks
 // KS >= the graph kind's in-degree bound).
 // ---------------------------------------------------------------------------
-template <typename T, int KS>
-__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
+template <typename T, int KS, bool WGT = false>
+__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
   const AggArgs& a = m.a;
   extern __shared__ float4 smem_f4[];
   const AttnLds L(smem_f4, a.nmax, kAttnFwdChunk, false);
@@ -278,6 +315,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p = tile * kAttnTile + lane;
   const bool pin = p < a.P;
+  if constexpr (WGT) attn_stage_w(m, L, node0, n, p, pin);
   attn_tables(m, L, b, node0, n);
   constexpr int CK = kAttnFwdChunk;
   const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
@@ -299,12 +337,53 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
 
   // softmax over the row's entries, in registers; s becomes the weights
   constexpr float kLog2e = 1.4426950408889634f;
+  unsigned dmask[kAttnDpw];  // WGT: bit j: entry j of destination i delivered at this lane's pixel
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) dmask[i] = 0u;
 #pragma unroll
   for (int i = 0; i < kAttnDpw; ++i) {
     const int v = wave + kAttnWaves * i;
     if (v >= n) continue;
     const int deg = __builtin_amdgcn_readfirstlane(L.rowlen[v]);
     float mx = -__builtin_inff();
+    if constexpr (WGT) {
+      // the gated softmax: max and sum over the delivered entries of this lane's pixel; u_j = exp(s_j - mx) for
+      // every entry (a silent one's goes to rate only)
+      const AttnRow r(L, v);
+      const float* Wl = attn_wt(L, a.nmax) + lane;
+      unsigned dl = 0u;
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        if (jj >= deg) continue;
+        s[i][jj] = __fmul_rn(m.scale, s[i][jj]);
+        const bool d = Wl[r.src(jj) * kAttnTile] > 0.f;  // false for a negative or NaN weight
+        dl |= d ? 1u << jj : 0u;
+        mx = d ? fmaxf(mx, s[i][jj]) : mx;
+      }
+      float z = 0.f;
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        if (jj >= deg) continue;
+        s[i][jj] = __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(s[i][jj], mx), kLog2e));
+        const float t = __fmul_rn(Wl[r.src(jj) * kAttnTile], s[i][jj]);
+        z = (dl >> jj) & 1u ? __fadd_rn(z, t) : z;
+      }
+      const bool zpos = dl != 0u && z > 0.f;  // nobody delivered: mx = -inf and the u_j mean nothing
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        if (jj >= deg) continue;
+        const float u = s[i][jj];
+        const float t = __fmul_rn(Wl[r.src(jj) * kAttnTile], u);
+        s[i][jj] = zpos && ((dl >> jj) & 1u) ? __fdiv_rn(t, z) : 0.f;
+        const int e = L.slot_e[v * kAttnSlots + jj];
+        if (pin) {
+          m.attn[(int64_t)e * a.P + p] = s[i][jj];
+          if (m.rate != nullptr) m.rate[(int64_t)e * a.P + p] = zpos ? __fdiv_rn(u, z) : 0.f;
+        }
+      }
+      dmask[i] = dl;
+      continue;
+    }
 #pragma unroll
     for (int jj = 0; jj < KS; ++jj) {
       if (jj >= deg) continue;
@@ -345,12 +424,25 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
         float xu[KS];
         attn_slots<KS>(Xc, Wc, r, w, xu);
         Frag<1> o;
+        if constexpr (WGT) {
+          // fma onto -0 is the bare product, sign of zero included: the chain starts at the lane's first
+          // delivered entry as film_attn's starts at slot 0
+          o.v[0] = -0.f;
+#pragma unroll
+          for (int jj = 0; jj < KS; ++jj) {
+            const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
+            const float t = __fmaf_rn(s[i][jj], msg, o.v[0]);
+            o.v[0] = (dmask[i] >> jj) & 1u ? t : o.v[0];  // a per-lane select: a silent entry is never multiplied
+          }
+          o.v[0] = dmask[i] != 0u ? o.v[0] : 0.f;  // nobody delivered (or an empty row): an exact zero
+        } else {
         o.v[0] = 0.f;  // empty row: zeros
 #pragma unroll
         for (int jj = 0; jj < KS; ++jj) {
           const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
           const float t = jj == 0 ? __fmul_rn(s[i][jj], msg) : __fmaf_rn(s[i][jj], msg, o.v[0]);
           o.v[0] = jj < r.deg ? t : o.v[0];  // a select, not a branch (wave-uniform)
+        }
         }
         if (pin) store_frag<1, true>(ob + (int64_t)cl * a.P, o);
       }
@@ -362,8 +454,8 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgs m) {
 // Backward.  Workgroup = graph x pixel tile; a.want_dx / a.want_dgb choose the outputs (the arithmetic of
 // either is the same whether or not the other is wanted).  CK: channels per chunk; KS as in the forward.
 // ---------------------------------------------------------------------------
-template <typename T, int CK, int KS>
-__global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
+template <typename T, int CK, int KS, bool WGT = false>
+__global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
   const AggArgs& a = m.a;
   extern __shared__ float4 smem_f4[];
   const AttnLds L(smem_f4, a.nmax, CK, true);
@@ -375,6 +467,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p = tile * kAttnTile + lane;
   const bool pin = p < a.P;
+  if constexpr (WGT) attn_stage_w(m, L, node0, n, p, pin);
   attn_tables(m, L, b, node0, n);
   const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
   AttnChunk<CK, true, T> next;
@@ -393,12 +486,60 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
     attn_fetch<CK, true, T>(m, node0, n, last ? 0 : c0 + CK, p, pin, my_e, next, last);
     attn_scores<true, KS>(m, L, n, min(CK, a.C - c0), ds);
   }
+  unsigned dmask[kAttnDpw];  // WGT: bit j: entry j of destination i delivered at this lane's pixel
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) dmask[i] = 0u;
+  if constexpr (WGT) {
+    // grad_w's cells, one per (node, pixel), in the grad_x partials' space (unused until sweep B)
+    if (m.gw != nullptr) {
+      for (int t = threadIdx.x; t < n * kAttnTile; t += blockDim.x) L.D[t] = 0.f;
+      __syncthreads();
+    }
+  }
   // ds_j = a_j (da_j - sum_k a_k da_k), kept multiplied by scale (both of its uses are); zeros past the row's end
 #pragma unroll
   for (int i = 0; i < kAttnDpw; ++i) {
     const int v = wave + kAttnWaves * i;
     const int deg = v < n ? __builtin_amdgcn_readfirstlane(L.rowlen[v]) : 0;
     float dot = 0.f;
+    if constexpr (WGT) {
+      // the sum runs over the delivered entries, ds of a silent entry is 0; the silent entries' da_j are kept
+      // for grad_w
+      const AttnRow r(L, v < n ? v : 0);
+      unsigned dl = 0u;
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        if (jj >= deg) continue;
+        const int e = L.slot_e[v * kAttnSlots + jj];
+        at[i][jj] = pin ? m.attn[(int64_t)e * a.P + p] : 0.f;
+        const bool d = attn_wt(L, a.nmax)[r.src(jj) * kAttnTile + lane] > 0.f;
+        dl |= d ? 1u << jj : 0u;
+        dot = d ? __fmaf_rn(at[i][jj], ds[i][jj], dot) : dot;
+      }
+      dmask[i] = dl;
+      if (m.gw != nullptr) {
+        // grad_w[u_j] += r_j (da_j - dbar), destinations ascending: v = 4 i + t is wave t's, the waves take turns
+#pragma unroll
+        for (int t = 0; t < kAttnWaves; ++t) {
+          if (kAttnWaves * i + t >= n) continue;  // workgroup-uniform
+          if (wave == t) {
+#pragma unroll
+            for (int jj = 0; jj < KS; ++jj) {
+              if (jj >= deg) continue;
+              const int e = L.slot_e[v * kAttnSlots + jj];
+              const float rt = pin ? m.rate[(int64_t)e * a.P + p] : 0.f;
+              float* cell = L.D + r.src(jj) * kAttnTile + lane;
+              *cell = __fmaf_rn(rt, __fsub_rn(ds[i][jj], dot), *cell);
+            }
+          }
+          __syncthreads();
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj)
+        ds[i][jj] = (dl >> jj) & 1u ? __fmul_rn(m.scale, __fmul_rn(at[i][jj], __fsub_rn(ds[i][jj], dot))) : 0.f;
+      continue;
+    }
 #pragma unroll
     for (int jj = 0; jj < KS; ++jj) {
       if (jj >= deg) continue;
@@ -411,8 +552,19 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
       ds[i][jj] = jj < deg ? __fmul_rn(m.scale, __fmul_rn(at[i][jj], __fsub_rn(ds[i][jj], dot))) : 0.f;
   }
 
+  if constexpr (WGT) {
+    // grad_w of the nodes this wave stages (every node of the graph is written: zeros for one nobody hears);
+    // sweep B's first barrier precedes the next write to these cells
+    if (m.gw != nullptr && pin)
+      for (int u = wave; u < n; u += kAttnWaves)
+        m.gw[(int64_t)(node0 + u) * m.gwst + p] = L.D[u * kAttnTile + lane];
+  }
+
   // sweep B
   const bool want_dx = a.want_dx != 0, want_dgb = a.want_dgb != 0;
+  if constexpr (WGT) {
+    if (!want_dx && !want_dgb) return;  // grad_w alone (whole workgroup): done
+  }
   for (int c0 = 0; c0 < a.C; c0 += CK) {
     const int ck = min(CK, a.C - c0);
     attn_put<CK, true, T>(m, L, n, my_e, next);
@@ -444,7 +596,8 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
         float qacc = 0.f;  // the query path: scale sum_j ds_j m_j
 #pragma unroll
         for (int jj = 0; jj < KS; ++jj) {
-          const bool used = jj < r.deg;  // wave-uniform; selects, not branches
+          // wave-uniform; selects, not branches (WGT: per lane, the delivered entries)
+          const bool used = WGT ? ((dmask[i] >> jj) & 1u) != 0u : jj < r.deg;
           const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
           float dm = __fmaf_rn(ds[i][jj], xv, __fmul_rn(at[i][jj], g));  // key path + value path
           dm = used ? dm : 0.f;
@@ -452,11 +605,14 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
           if (want_dx) {
             // (gamma, dm) = (0, 0) past the row's end: the partial of node 0 is rewritten unchanged
             float* Du = Dc + r.src(jj) * kAttnTile;
-            *Du = __fmaf_rn(w[jj].x, dm, *Du);
+            if constexpr (WGT)
+              *Du = used ? __fmaf_rn(w[jj].x, dm, *Du) : *Du;
+            else
+              *Du = __fmaf_rn(w[jj].x, dm, *Du);
           }
           if (want_dgb) {
             float2 rsum = make_float2(wave_sum63(used ? __fmul_rn(xu[jj], dm) : 0.f), wave_sum63(dm));
-            if (lane == 63 && used) {
+            if (lane == 63 && jj < r.deg) {
               const int e = L.slot_e[v * kAttnSlots + jj];
               const int64_t off = ((int64_t)e * a.C + c) * 2;
               if (m.ntile > 1) {
@@ -500,15 +656,16 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgs m) {
 namespace mrp_host {
 
 using mrp::AttnArgs;
+using mrp::WAttnArgs;
 
 inline int attn_tiles(int32_t P) { return (P + mrp::kAttnTile - 1) / mrp::kAttnTile; }
 
 inline int attn_bwd_chunk(int max_nodes) { return max_nodes <= 8 ? mrp::kAttnBwdChunkSmall : mrp::kAttnBwdChunk; }
 
-inline size_t lds_attn(int nmax, int ck, bool bwd) {
+inline size_t lds_attn(int nmax, int ck, bool bwd, bool weighted = false) {
   return (size_t)ck * nmax * mrp::kAttnTile * 4 * (bwd ? 2 + mrp::kAttnWaves : 1) +
          (size_t)ck * nmax * mrp::kAttnSlots * 8 + (size_t)nmax * 8 + (size_t)nmax * mrp::kAttnSlots * 4 +
-         (size_t)nmax * 4;
+         (size_t)nmax * 4 + (weighted ? (size_t)nmax * mrp::kAttnTile * 4 : 0);
 }
 
 // bytes of the backward's grad_gb workspace
@@ -542,11 +699,17 @@ inline int attn_slots_for(int32_t graph_kind, int32_t max_nodes) {
 hipError_t launch_attn_bwd_f32(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
 hipError_t launch_attn_bwd_bf16(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
 hipError_t launch_attn_bwd_f16(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+// the confidence-gated instantiations (film_wattn_bwd*.hip)
+hipError_t launch_wattn_bwd_f32(const WAttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+hipError_t launch_wattn_bwd_bf16(const WAttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+hipError_t launch_wattn_bwd_f16(const WAttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st);
+// film_attn_dgb_reduce (film_attn_bwd.hip) over `blocks` workgroups
+hipError_t launch_attn_dgb_reduce(const AttnArgs& m, int64_t blocks, hipStream_t st);
 
-template <typename T>
-hipError_t launch_attn_bwd(const AttnArgs& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st) {
+template <typename T, bool WGT = false>
+hipError_t launch_attn_bwd(const mrp::AttnArgsOf<WGT>& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st) {
   const dim3 g((unsigned)grid), block(mrp::kBlock);
-#define MRP_ATTN_BWD(CK, KS) hipLaunchKernelGGL((mrp::film_attn_bwd<T, CK, KS>), g, block, lds, st, m)
+#define MRP_ATTN_BWD(CK, KS) hipLaunchKernelGGL((mrp::film_attn_bwd<T, CK, KS, WGT>), g, block, lds, st, m)
   if (ck == mrp::kAttnBwdChunkSmall) {  // <= 8 nodes: in-degree <= 8 for every kind but CSR / SIMPLE rows
     if (ks == 4)
       MRP_ATTN_BWD(mrp::kAttnBwdChunkSmall, 4);

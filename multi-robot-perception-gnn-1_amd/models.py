@@ -27,7 +27,9 @@ Semantics switch ``opt.gcn_return``:
 ``fn.copy_u`` variant, ``models.py:225``), ``'film_sum'``, ``'film_max'`` (``node_udf`` =
 ``torch.max(mailbox, 1)``: :func:`aggregate.film_max`, every in-degree <= 16), ``'film_attn'`` (per-location
 attention over the messages: :func:`aggregate.film_attn`, every in-degree <= 16; ``opt.gcn_attn_scale``
-sets the score scale, default ``None``: 1/sqrt(C)).
+sets the score scale, default ``None``: 1/sqrt(C)), ``'film_wattn'`` (the same attention over what each sender's
+confidence map delivered: :func:`aggregate.film_wattn`, with the maps of ``opt.gcn_confidence`` or ``weights=``;
+with neither it is ``'film_attn'`` itself, same kernels, same bits).
 
 ``opt.gcn_message_dtype``: ``None`` (default: nothing changes), ``'fp8_e4m3'`` or ``'fp8_e5m2'`` — the
 feature maps every GCN layer aggregates are quantised per node to OCP FP8, as each robot would transmit them
@@ -42,7 +44,8 @@ handed FP8 buffers (:func:`aggregate.film_mean_q`).  See :meth:`GCN._aggregate_q
 the receiver averages, pixel by pixel, over what was delivered (:func:`aggregate.film_wmean`; Where2comm-style
 sparse messaging).  ``opt.gcn_confidence_threshold = tau`` hard-gates the map (``w < tau`` is not transmitted:
 0; the gradient flows through the kept values).  Every ``GCN`` method also takes ``weights=`` to supply a map
-(N, H, W) directly.  Modes ``film_mean``, ``film_sum`` and ``copy_mean``; combined with ``film_max``,
+(N, H, W) directly.  Modes ``film_mean``, ``film_sum`` and ``copy_mean`` average (:func:`aggregate.film_wmean`);
+``film_wattn`` attends over what was delivered (:func:`aggregate.film_wattn`); combined with ``film_max``,
 ``film_attn`` or ``gcn_message_dtype`` a ``ValueError`` is raised when the module is built.
 """
 from __future__ import annotations
@@ -54,6 +57,7 @@ import torch.nn as nn
 
 from .aggregate import (film_mean_fq, film_mean_q, film_mean_q_forward_into, quantize_features)
 from .aggregate import film_wmean, film_wmean_cat, film_wmean_mix, film_wmean_residual
+from .aggregate import film_wattn, film_wattn_cat, film_wattn_mix, film_wattn_residual
 from .aggregate import (film_attn, film_attn_cat, film_attn_mix, film_attn_residual, film_max, film_max_cat,
                         film_max_mix, film_max_residual, film_mean, film_mean_cat, film_mean_mix, film_mean_residual)
 from .compress import CompressFunction, compress_1x1, compress_path, film_compress, film_compress_supported
@@ -156,7 +160,7 @@ def _check_weighted(opt) -> None:
     mode = _opt(opt, "gcn_mode", "film_mean")
     if mode in ("film_max", "film_attn"):
         raise ValueError(f"confidence-weighted aggregation is not provided for gcn_mode={mode!r} "
-                         "(film_mean, film_sum, copy_mean)")
+                         "(film_mean, film_sum, copy_mean, film_wattn)")
     if _opt(opt, "gcn_message_dtype", None) is not None:
         raise ValueError("confidence-weighted aggregation is not provided together with gcn_message_dtype")
 
@@ -172,7 +176,10 @@ class GCN(_PackedImages, nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        message_format(opt)  # an unknown gcn_message_dtype / gcn_message_scale: ValueError here
+        fmt = message_format(opt)[0]  # an unknown gcn_message_dtype / gcn_message_scale: ValueError here
+        if fmt is not None and _opt(opt, "gcn_mode", "film_mean") == "film_wattn":
+            raise ValueError("gcn_message_dtype is not provided for gcn_mode='film_wattn' "
+                             "(film_mean, film_sum, copy_mean)")
         self.edge_encoder = edge_encoder(layers_dim=[opt.feature_dim, opt.feature_dim])
         if confidence_options(opt)[0]:  # a forbidden combination: ValueError here
             self.confidence = nn.Conv2d(opt.feature_dim, 1, kernel_size=1)
@@ -220,6 +227,15 @@ class GCN(_PackedImages, nn.Module):
             return weights
         return self.confidence_map(x) if "confidence" in self._modules else None
 
+    def _wattn(self) -> bool:
+        """``opt.gcn_mode == 'film_wattn'``: sender maps gate the attention (:func:`aggregate.film_wattn`);
+        without maps every branch below takes ``film_attn``'s route."""
+        return _opt(self.opt, "gcn_mode", "film_mean") == "film_wattn"
+
+    def _wattn_args(self, g, x, w):
+        """The leading arguments of ``film_wattn*``: features, logits, maps, graph."""
+        return x, self.edge_encoder.logits(g.edata["pose"]), w, g.csr(x.device)
+
     def _wmean_args(self, g, x):
         """(gb or logits, csr, mode, logits?) of the weighted aggregation for ``opt.gcn_mode``; ``copy_mean`` is
         gamma = 1, beta = 0, materialised."""
@@ -239,7 +255,7 @@ class GCN(_PackedImages, nn.Module):
         quantise pass costs more than the aggregation saves; the option is for evaluating and training
         models for 8-bit links, and the saving belongs to a receiver that is handed FP8 buffers."""
         mode = _opt(self.opt, "gcn_mode", "film_mean")
-        if mode in ("film_max", "film_attn"):
+        if mode in ("film_max", "film_attn", "film_wattn"):
             raise ValueError(f"gcn_message_dtype is not provided for gcn_mode={mode!r} (film_mean, film_sum, copy_mean)")
         if self._return_mode() == "input":
             raise ValueError("gcn_message_dtype with gcn_return='input': no message is aggregated")
@@ -267,6 +283,8 @@ class GCN(_PackedImages, nn.Module):
         if self._return_mode() == "input":
             return x  # models.py:226 returns the input; update_all's result is never read
         if w is not None:
+            if self._wattn():
+                return film_wattn(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean(x, gb, w, csr, wmode, logits=logits)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -276,7 +294,7 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":  # the max reducer: an operator of its own (aggregate.film_max)
             return film_max(x, z, g.csr(x.device), logits=True)
-        if mode == "film_attn":  # per-location attention over the messages (aggregate.film_attn)
+        if mode in ("film_attn", "film_wattn"):  # per-location attention over the messages (aggregate.film_attn)
             return film_attn(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean(x, z, g.csr(x.device), mode, logits=True)
 
@@ -295,6 +313,8 @@ class GCN(_PackedImages, nn.Module):
             cat[:, :C].copy_(x)
             return cat
         if w is not None and self._return_mode() != "input":
+            if self._wattn():
+                return film_wattn_cat(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_cat(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -305,7 +325,7 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_cat(x, z, g.csr(x.device), logits=True)
-        if mode == "film_attn":
+        if mode in ("film_attn", "film_wattn"):
             return film_attn_cat(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
@@ -339,6 +359,8 @@ class GCN(_PackedImages, nn.Module):
                 return CompressFunction.apply(x, a, conv.weight, conv.bias)
             return compress_1x1(conv, torch.cat((x, a), dim=1))
         if w is not None and self._return_mode() != "input":
+            if self._wattn():  # the cat kernel, then the compress reading the buffer's two halves in place
+                return compress_1x1(conv, self.forward_cat(g, x, weights=w))
             if x.is_cuda and compress_path() != "library" and film_compress_supported(conv, x):
                 gb, csr, wmode, logits = self._wmean_args(g, x)
                 flags = _lib_modes()["film_sum" if wmode == "sum" else "film_mean"] | (_lib_logits() if logits else 0)
@@ -352,7 +374,7 @@ class GCN(_PackedImages, nn.Module):
             z = self.edge_encoder.logits(g.edata["pose"])
             if mode == "film_max":
                 return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="max")
-            if mode == "film_attn":
+            if mode in ("film_attn", "film_wattn"):
                 return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="attn",
                                      scale=self._attn_scale())
             return film_compress(conv, x, z, g.csr(x.device), _lib_modes()[mode] | _lib_logits())
@@ -367,6 +389,8 @@ class GCN(_PackedImages, nn.Module):
         if fmt is not None:  # the layer's own h through the epilogue's x0, unquantised
             return self._aggregate_q(g, x, fmt, per, x0=x, x0_scale=1.0)
         if w is not None and self._return_mode() != "input":
+            if self._wattn():
+                return film_wattn_residual(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_residual(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -377,7 +401,7 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_residual(x, z, g.csr(x.device), logits=True)
-        if mode == "film_attn":
+        if mode in ("film_attn", "film_wattn"):
             return film_attn_residual(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
         return film_mean_residual(x, z, g.csr(x.device), mode, logits=True)
 
@@ -391,6 +415,8 @@ class GCN(_PackedImages, nn.Module):
         if fmt is not None:
             return self._aggregate_q(g, x, fmt, per, x0=x0, agg_scale=1.0 - float(alpha), x0_scale=float(alpha))
         if w is not None and self._return_mode() != "input":
+            if self._wattn():
+                return film_wattn_mix(*self._wattn_args(g, x, w), x0, alpha, logits=True, scale=self._attn_scale())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_mix(x, gb, w, csr, x0, alpha, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -401,7 +427,7 @@ class GCN(_PackedImages, nn.Module):
         z = self.edge_encoder.logits(g.edata["pose"])
         if mode == "film_max":
             return film_max_mix(x, z, g.csr(x.device), x0, alpha, logits=True)
-        if mode == "film_attn":
+        if mode in ("film_attn", "film_wattn"):
             return film_attn_mix(x, z, g.csr(x.device), x0, alpha, logits=True, scale=self._attn_scale())
         return film_mean_mix(x, z, g.csr(x.device), x0, alpha, mode, logits=True)
 

@@ -439,17 +439,26 @@ def _mode_flags(mode, logits: bool) -> int:
 
 def launch_plan(direction: str, graph, C: int, P: int, dtype=torch.float32, mode="film_mean", logits: bool = False,
                 align: int = 16, grad_x_base: bool = False, need_dx: bool = True, need_dgb: bool = True,
-                x0: bool = False, xcopy: bool = False, stride: Optional[int] = None) -> _lib.AggPlan:
+                x0: bool = False, xcopy: bool = False, stride: Optional[int] = None,
+                strides: Optional[dict] = None) -> _lib.AggPlan:
     """The launch plan (``mrp_film_mean_fwd_plan`` / ``_bwd_plan``: kernel, slice width, lanes per plane,
     channels per workgroup, LDS ...) of the ``"fwd"`` or ``"bwd"`` aggregation under the current tuning
     knobs, for dense (N, C, H*W = P) tensors whose storage is aligned to ``align`` bytes.  ``graph`` is
     anything with ``num_graphs``, ``max_nodes``, ``graph_kind``, ``num_nodes`` and ``num_edges`` (a
     ``GraphCSR``).  Host-only: no tensor is needed and no GPU call is made — the library looks at pointers
-    for their alignment alone, so made-up ones stand in.  x0 / xcopy: the forward epilogue's extra tensors."""
+    for their alignment alone, so made-up ones stand in.  x0 / xcopy: the forward epilogue's extra tensors.
+    ``stride``: every tensor's node stride in elements (default dense, C * P); ``strides``: the backward's
+    operands that have another one, by name (``"grad_out"``, ``"x"``, ``"grad_x"``, ``"base"``)."""
     base = 1 << 20
     p = ctypes.c_void_p(base if align % 16 == 0 else base + align)
     null = ctypes.c_void_p(0)
     ns = C * P if stride is None else stride
+    strides = dict(strides or {})
+    if direction != "bwd" and strides:
+        raise ValueError("per-operand strides are the backward's")
+    gs, xs, gxs, bs = (strides.pop(k, ns) for k in ("grad_out", "x", "grad_x", "base"))
+    if strides:
+        raise ValueError(f"unknown operands {sorted(strides)}")
     m = _mode_flags(mode, logits)
     copy = (m & ~_lib.GB_LOGITS) == _lib.MODE_COPY_MEAN
     args = (null if copy else p, p, p, p, p, graph.num_graphs, graph.max_nodes, graph.graph_kind, graph.num_nodes,
@@ -464,8 +473,8 @@ def launch_plan(direction: str, graph, C: int, P: int, dtype=torch.float32, mode
                                           ctypes.byref(ep) if ep is not None else None, ctypes.byref(plan))
         _lib.check(code, "mrp_film_mean_fwd_plan")
     elif direction == "bwd":
-        code = lib.mrp_film_mean_bwd_plan(FEATURE_DTYPES[dtype], p, ns, p, ns, *args, p if need_dx else null, ns,
-                                          p if (grad_x_base and need_dx) else null, ns, p if need_dgb else null,
+        code = lib.mrp_film_mean_bwd_plan(FEATURE_DTYPES[dtype], p, gs, p, xs, *args, p if need_dx else null, gxs,
+                                          p if (grad_x_base and need_dx) else null, bs, p if need_dgb else null,
                                           None, ctypes.byref(plan))
         _lib.check(code, "mrp_film_mean_bwd_plan")
     else:

@@ -1,7 +1,9 @@
 """Shared by test_geometry_cpu.py and test_gpu_geometry.py: the tuning knobs' accepted ranges (read from the
 table in ``mrp_tuning_set``), a context manager that sets knobs and restores every default, what the
 aggregation kernels require of a launch plan (``violations``: each requirement beside the line of kernel
-source it comes from), and the table of GPU cases (``ROWS``).
+source it comes from), the table of GPU cases (``ROWS``), and — for ``film_max_fwd`` and ``film_wmean_fwd``, which
+are sized by film_fwd's knobs but have no plan query — a mirror of the planner's ``make_geometry`` with a table of
+their own (``FWD_ROWS``).
 
 A launch plan is what ``mrp_film_mean_fwd_plan`` / ``mrp_film_mean_bwd_plan`` report (``aggregate.launch_plan``):
 the launchers act on the very same planner, so a plan that holds every requirement here is a launch that
@@ -294,4 +296,106 @@ ROWS = [
     # ---- default knobs: the Gram pass of complete 16-node graphs with logits at C >= 16 asked for 67,392
     # bytes of LDS (a launch error) before the planner halved its channels
     R("d01", "complete", (16, 16), 17, 4, 4, {}, bwd=(DXG, 4, 4, 8), logits=True),
+]
+
+
+# ------------------------------------------------------------------ film_max_fwd and film_wmean_fwd under the knobs
+# Both size their launch with "make_geometry(C, P, vec, tu.fwd_lo, tu.fwd_hi, tu.fwd_cap)" (film_max_fwd.hip,
+# film_wmean_fwd.hip), film_fwd's knobs, and have no plan query.  ``make_geometry`` below restates the planner
+# (test_geometry_cpu.py holds it equal to what mrp_film_mean_fwd_plan reports for film_fwd over the knobs' ranges, and
+# pins the restated lines to the source); ``forward_geometry`` adds each launcher's slice width and plane split.
+MAKE_GEOMETRY_SOURCE = [  # film_mean_kernels.hpp, make_geometry
+    "const int pv = P / g.vec;",
+    "const int target = std::min(std::max(pv / 2, lo), hi);",
+    "int lpc = 1;",
+    "while (lpc * 2 <= pv && lpc * 2 <= target) lpc *= 2;",
+    "int cpb = mrp::kBlock / lpc;",
+    "if (cpb > max_cpb) cpb = max_cpb;",
+    "if (cpb > C) cpb = C;",
+    "g.threads = cpb * lpc;",
+    "g.ncb = (C + cpb - 1) / cpb;",
+]
+KBLOCK = 256  # "constexpr int kBlock = 256;"
+
+
+def make_geometry(C, P, vec, lo, hi, cap):
+    """(lpc, cpb, threads, ncb): MAKE_GEOMETRY_SOURCE, line for line."""
+    pv = P // vec
+    target = min(max(pv // 2, lo), hi)
+    lpc = 1
+    while lpc * 2 <= pv and lpc * 2 <= target:
+        lpc *= 2
+    cpb = KBLOCK // lpc
+    if cpb > cap:
+        cpb = cap
+    if cpb > C:
+        cpb = C
+    return lpc, cpb, cpb * lpc, (C + cpb - 1) // cpb
+
+
+def forward_geometry(row, lo=16, hi=64, cap=16):
+    """(vec, lpc, cpb, psplit) of a FWD_ROWS row's launch on dense, 16-byte aligned x and out under the given knobs
+    (defaults: "int fwd_lo = 16", "fwd_hi = 64", "fwd_cap = 16" of tuning.hpp).  Slice width, film_max_fwd.hip:
+    "if (elem == 2 && max_nodes <= 8 && sc.ok(8, elem)) vec = 8; else if (sc.ok(4, elem)) vec = 4;";
+    film_wmean_fwd.hip: "sc.ok(4, elem) && aligned16(w) && w_node_stride % 4 == 0 ? 4 : 1".  Plane split, both:
+    "g.psplit = graph_kind == MRP_GRAPH_COMPLETE ? (pv + g.lpc - 1) / g.lpc : 1;"."""
+    P = row.H * row.W
+    if row.family == "max":
+        vec = 8 if ELEM[row.key] == 2 and max(row.ns) <= 8 and P % 8 == 0 else 4 if P % 4 == 0 else 1
+    else:
+        vec = 4 if P % 4 == 0 and not row.w_odd else 1
+    lpc, cpb, _, _ = make_geometry(row.C, P, vec, lo, hi, cap)
+    pv = P // vec
+    return vec, lpc, cpb, (pv + lpc - 1) // lpc if row.kind == "complete" else 1
+
+
+# A row: the family, a batch of two graphs (CSR / k-NN: the second smaller), C with a ragged last channel block, the
+# smallest plane that gives the row's lanes, the knobs, and the (vec, lpc, cpb, psplit) they are meant to reach —
+# written by hand; test_geometry_cpu.py holds them equal to ``forward_geometry``.  ``mode``: film_wmean's; ``w_odd``:
+# w with a node stride of P + 1 elements, which allows x 4-element slices but not w.
+FwdRow = collections.namedtuple("FwdRow", "name family kind ns C H W key knobs geo mode w_odd")
+
+
+def F(name, family, kind, ns, C, H, W, knobs, geo, key="f32", mode="mean", w_odd=False):
+    return FwdRow(name, family, kind, ns, C, H, W, key, knobs, geo, mode, w_odd)
+
+
+def LH(lanes):
+    return dict(fwd_lo=lanes, fwd_hi=lanes)
+
+
+FWD_ROWS = [
+    # ---- film_max_fwd
+    F("x01", "max", "complete", (5, 5), 19, 4, 4, LH(1), (4, 1, 16, 4)),  # one lane, the plane in 4 segments
+    F("x02", "max", "csr", (8, 5), 19, 4, 4, LH(2), (4, 2, 16, 1)),  # a lane walks 2 slices
+    F("x03", "max", "csr", (16, 9), 19, 8, 8, LH(4), (4, 4, 16, 1)),  # a lane walks 4 slices
+    F("x04", "max", "complete", (8, 8), 7, 16, 16, LH(64), (4, 64, 4, 1)),
+    F("x05", "max", "knn4", (16, 12), 5, 32, 16, LH(128), (4, 128, 2, 1)),
+    F("x06", "max", "complete", (4, 4), 4, 32, 32, LH(256), (4, 256, 1, 1)),
+    # 20 slices on 8 lanes: 3 segments, the last ragged (6 x 8 on 8 lanes is ragged too, but is the default plan)
+    F("x07", "max", "complete", (8, 8), 19, 8, 10, LH(8), (4, 8, 16, 3)),
+    F("x08", "max", "complete", (3, 3), 4, 8, 8, dict(fwd_cap=1), (4, 16, 1, 1)),
+    F("x09", "max", "csr", (8, 6), 7, 8, 8, dict(fwd_cap=3), (4, 16, 3, 1)),
+    F("x10", "max", "knn4", (8, 6), 19, 8, 8, dict(fwd_cap=16, fwd_lo=64, fwd_hi=4), (4, 4, 16, 1)),  # lo > hi
+    F("x11", "max", "csr", (5, 3), 19, 4, 4, dict(fwd_lo=3, fwd_hi=100), (4, 2, 16, 1)),  # no powers of two
+    F("x12", "max", "csr", (16, 11), 19, 5, 5, LH(4), (1, 4, 16, 1)),  # 1-element slices
+    F("x13", "max", "complete", (8, 8), 19, 8, 8, LH(4), (8, 4, 16, 2), key="bf16"),  # 8-element slices
+    F("x14", "max", "knn4", (16, 12), 19, 8, 8, LH(4), (4, 4, 16, 1), key="f16"),
+    F("x15", "max", "complete", (16, 16), 19, 4, 4, LH(1), (4, 1, 16, 4), key="bf16"),
+    # ---- film_wmean_fwd
+    F("w01", "wmean", "complete", (5, 5), 19, 4, 4, LH(1), (4, 1, 16, 4)),
+    F("w02", "wmean", "csr", (8, 5), 19, 4, 4, LH(2), (4, 2, 16, 1), mode="sum"),
+    F("w03", "wmean", "knn4", (16, 9), 19, 8, 8, LH(4), (4, 4, 16, 1)),
+    F("w04", "wmean", "complete", (8, 8), 7, 16, 16, LH(64), (4, 64, 4, 1), mode="sum"),
+    F("w05", "wmean", "csr", (16, 9), 5, 32, 16, LH(128), (4, 128, 2, 1)),
+    F("w06", "wmean", "complete", (4, 4), 4, 32, 32, LH(256), (4, 256, 1, 1)),
+    F("w07", "wmean", "complete", (8, 8), 19, 8, 10, LH(8), (4, 8, 16, 3), mode="sum"),
+    F("w08", "wmean", "complete", (3, 3), 4, 8, 8, dict(fwd_cap=1), (4, 16, 1, 1)),
+    F("w09", "wmean", "csr", (8, 6), 7, 8, 8, dict(fwd_cap=3), (4, 16, 3, 1), mode="sum"),
+    F("w10", "wmean", "knn4", (8, 6), 19, 8, 8, dict(fwd_cap=16, fwd_lo=64, fwd_hi=4), (4, 4, 16, 1)),
+    F("w11", "wmean", "csr", (5, 3), 19, 4, 4, dict(fwd_lo=3, fwd_hi=100), (4, 2, 16, 1)),
+    F("w12", "wmean", "csr", (16, 11), 19, 5, 5, LH(4), (1, 4, 16, 1)),
+    F("w13", "wmean", "complete", (8, 8), 19, 8, 8, LH(4), (4, 4, 16, 4), key="bf16"),
+    F("w14", "wmean", "knn4", (16, 12), 19, 8, 8, LH(4), (4, 4, 16, 1), key="f16", mode="sum"),
+    F("w15", "wmean", "complete", (8, 8), 19, 8, 8, LH(4), (1, 4, 16, 16), w_odd=True),  # w forces single elements
 ]

@@ -18,7 +18,12 @@ Tensor offsets are whole MiB slots (at most 63), so blocks of different tensors 
 blocks could only meet if a slot difference (< 64 MiB) equalled a multiple of S.  The encoder's row-strided
 matrices (h^T, dh^T: C rows; dz^T: 2C rows of E floats) are placed the same way, a row per "node", with the
 row stride ``2^27 bytes + 8 MiB``: row 16 is past 2 GiB, row 31 past 4 GiB, and dz^T's 64 rows end at
-8.4 GiB — which sets the working span.
+8.4 GiB — which sets the working span.  One aggregation case (``complete_1x16_s512``) has a stride of its own,
+``2^29 bytes + 64 KiB``: a single 16-node graph whose node 4 onward lies beyond 2^31 and node 8 onward beyond
+2^32 bytes *from the graph's own first node* (with S no graph reaches past 11 S = 2.75 GiB from its first node, so
+a 64-bit per-graph base with a 32-bit per-node offset would pass every other case); its 15 strides and the
+slots end inside the working span (asserted below).  The fp32 sender maps ``w`` / ``grad_w`` of the weighted
+families are placed like any feature tensor, as (n, 1, H, W).
 
 **Checker** (:meth:`Arena.check`): reads the outputs back, restores the sentinel over every region the
 call was allowed to write, compares the input blocks with their original bits and scans the whole arena:
@@ -206,15 +211,48 @@ COMPRESS = {
     "n18_c32_p49": (18, 32, 7, 7),     # 16-bit pixel-major: stages cross node boundaries
 }
 
-#: aggregation cases: name -> (graph sizes, k of k-NN or None, C, H, W, node stride in bytes beyond S)
+#: aggregation cases: name -> (graph sizes, k of k-NN or None, C, H, W, node stride in elements beyond the
+#: case's base stride)
 AGG = {
     "complete_3x8": ((8, 8, 8), None, 8, 8, 8, 0),
     "complete_2x12": ((12, 12), None, 8, 8, 8, 0),
     "knn4_2x12": ((12, 12), 4, 8, 8, 8, 0),
     "ragged_8_5_1_8": ((8, 5, 1, 8), None, 8, 8, 8, 0),
     "scalar_3x8_p15": ((8, 8, 8), None, 8, 3, 5, 1),  # P = 15 and an odd node stride (S + one element)
+    # P = 80: two 64-pixel attention tiles, the second ragged; C = 17: two channel blocks of 16, the second ragged
+    "wide_3x8_c17_p80": ((8, 8, 8), None, 17, 8, 10, 0),
+    # one graph that by itself spans 2^32 bytes: node 4 onward is more than 2^31 bytes, node 8 onward more than
+    # 2^32 bytes from the graph's first node (AGG_STRIDE)
+    "complete_1x16_s512": ((16,), None, 8, 8, 8, 0),
 }
+#: the first five: S is the stride, a graph's farthest node at most 11 S = 2.75 GiB from its first
+AGG_S = tuple(AGG)[:5]
+#: cases whose base node stride is not S: name -> bytes
+AGG_STRIDE = {"complete_1x16_s512": (1 << 29) + (64 << 10)}
 AGG_CL = ("complete_3x8", "knn4_2x12")
+#: the pixel-major span runs: those and the self-spanning graph
+AGG_CL_SPAN = AGG_CL + ("complete_1x16_s512",)
+#: the graph sets of the max / attention / weighted families' span tests: all seven
+AGG_FAMILIES = tuple(AGG)
+
+
+def agg_stride(case, es):
+    """Node stride in bytes of an aggregation case's tensor of ``es``-byte elements."""
+    return AGG_STRIDE.get(case, NODE_STRIDE) + AGG[case][5] * es
+
+
+def agg_node_offsets(case, es):
+    """[(byte offset of node i from its tensor's first node, from its own graph's first node)] of a case."""
+    s, out, first = agg_stride(case, es), [], 0
+    for k in AGG[case][0]:
+        out += [((first + i) * s, i * s) for i in range(k)]
+        first += k
+    return out
+
+
+# the self-spanning graph ends inside the working span: 15 strides, the last slot, one (C, H, W) fp32 block
+assert 15 * AGG_STRIDE["complete_1x16_s512"] + (MAX_SLOTS - 1) * SLOT + 8 * 8 * 8 * 4 <= WORK
+assert all(s % 16 == 0 for s in AGG_STRIDE.values())
 
 #: encoder cases: name -> (C, E); h^T / dh^T (C, E) and dz^T (2C, E) with rows ROW_STRIDE bytes apart
 ENCODER = {"enc_c32_e64": (32, 64)}
@@ -224,8 +262,11 @@ ENCODER = {"enc_c32_e64": (32, 64)}
 #: the last output block 17 S = 4.25 GiB from the first, 7 nodes 6 S = 1.5 GiB, 8 nodes 7 S = 1.75 GiB (9 nodes
 #: would be the first to decline: test_capi_large_span.py).  Nothing else here is declined:
 #: the fp32 MFMA kernels address one column tile's (or one split's) node range with 31-bit offsets, not the
-#: tensor's; the split-bf16, the pixel-major and the 16-bit weight-gradient kernels, the aggregation kernels
-#: and the encoder's row-strided kernels form 64-bit node / row addresses.
+#: tensor's; the split-bf16, the pixel-major and the 16-bit weight-gradient kernels, the aggregation kernels of
+#: every family (mean, max, attention, confidence-weighted, confidence-gated: rows added below the table) and
+#: the encoder's row-strided kernels form 64-bit node / row addresses.  The mean's matrix-core backward alone
+#: keeps 32-bit offsets across a graph's nodes, and where they do not fit (``complete_1x16_s512``) its launcher
+#: runs the VALU kernels instead: success, not a decline.
 EXPECTED = {
     ("mrp_compress_fwd", "f32", "n18_c32_p32"): 0,
     ("mrp_compress_bwd_data", "f32", "n18_c32_p32"): 0,
@@ -305,6 +346,17 @@ EXPECTED = {
     ("mrp_edge_encoder_bwd_t", "f32", "enc_c32_e64"): 0,
     ("mrp_edge_encoder_bwd_pose", "f32", "enc_c32_e64"): 0,
 }
+# The graph that spans 2^32 bytes by itself, mrp_film_mean_*: the header states no span limit for the typed and
+# the pixel-major mean entry points (the matrix-core backward's 32-bit lane offsets are the launcher's own affair:
+# where 15 node strides do not fit it must run the VALU kernels, not decline).
+EXPECTED.update({(e, k, "complete_1x16_s512"): 0 for k in DTYPES for e in (
+    "mrp_film_mean_fwd_t", "mrp_film_mean_bwd_t", "mrp_film_mean_fwd_cl", "mrp_film_mean_bwd_cl")})
+#: the max-pooled, attention-pooled, confidence-weighted and confidence-gated aggregations
+FAMILY_ENTRIES = {fam: (f"mrp_film_{fam}_fwd", f"mrp_film_{fam}_bwd") for fam in ("max", "attn", "wmean", "wattn")}
+# The header declares no span limit for any of the eight ("64-bit node offsets"; node strides are int64_t elements
+# and nothing is said to be declined for their size): every dtype, every graph set, 0.
+EXPECTED.update({(e, k, case): 0 for es in FAMILY_ENTRIES.values() for e in es for k in DTYPES
+                 for case in AGG_FAMILIES})
 
 
 def expected(entry, key, case):

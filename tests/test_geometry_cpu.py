@@ -19,6 +19,10 @@ What the enumeration found when it was written, and the planner now prevents (fi
 
 ``fwd_hi`` / ``fwd_regular_hi`` above 64 are sound: no lane of film_fwd / film_fwd_regular reads another's values.
 
+``film_max_fwd`` and ``film_wmean_fwd`` call the same ``make_geometry`` with film_fwd's knobs and have no plan query:
+``geometry_cases.make_geometry`` mirrors it (pinned to the source text, and held equal to the plan query's film_fwd
+plans over the knobs' ranges), and the hand-written geometries of ``geometry_cases.FWD_ROWS`` are held to the mirror.
+
 Also here: ``tile_of`` and ``xcd_remap`` (gemm_common.hpp), the GEMMs' workgroup -> tile order behind the
 ``gemm_group`` / ``nt_group`` knobs, restated in Python (pinned to the source text) and checked by brute force
 to be bijections.
@@ -257,6 +261,115 @@ def test_table_covers_what_it_must():
     assert {r.mode for r in gc.ROWS if r.fwd} == {"film_mean", "film_sum", "copy_mean"}
     assert {max(r.ns) for r in gc.ROWS if r.fwd and r.fwd[0] == "film_fwd"} >= {1, 5, 8, 16}
     assert {r.kind for r in gc.ROWS if r.fwd and r.fwd[0] == "film_fwd_regular"} == {"knn1", "knn4", "knn5", "knn8"}
+
+
+# ------------------------------------------------ film_max_fwd / film_wmean_fwd: the planner's mirror, the rows
+def _source(name):
+    return " ".join(open(os.path.join(gc.CSRC, name)).read().split())
+
+
+def test_make_geometry_mirror_is_the_source():
+    """The lines ``geometry_cases.make_geometry`` restates, in order, inside the planner; the two launchers' calls
+    of it, their slice widths and plane splits as ``forward_geometry`` quotes them; the knobs' defaults."""
+    text = _source("film_mean_kernels.hpp")
+    body = text[text.index("inline Geometry make_geometry(int C, int P, int vec, int lo, int hi, int max_cpb) {"):]
+    body = body[:body.index("return g;")]
+    at = 0
+    for line in gc.MAKE_GEOMETRY_SOURCE:
+        assert line in body[at:], line
+        at = body.index(line, at) + len(line)
+    assert f"constexpr int kBlock = {gc.KBLOCK};" in text
+    assert "int fwd_lo = 16, fwd_hi = 64, fwd_cap = 16;" in _source("tuning.hpp")
+    call = "Geometry g = make_geometry(C, P, vec, tu.fwd_lo, tu.fwd_hi, tu.fwd_cap);"
+    split = "g.psplit = graph_kind == MRP_GRAPH_COMPLETE ? (pv + g.lpc - 1) / g.lpc : 1;"
+    fmax, fwmean = _source("film_max_fwd.hip"), _source("film_wmean_fwd.hip")
+    assert call in fmax and call in fwmean and split in fmax and split in fwmean
+    assert "int vec = 1; if (elem == 2 && max_nodes <= 8 && sc.ok(8, elem)) vec = 8; else if (sc.ok(4, elem)) vec = 4;" \
+        in fmax
+    assert "const int vec = sc.ok(4, elem) && aligned16(w) && w_node_stride % 4 == 0 ? 4 : 1;" in fwmean
+
+
+def _film_fwd_planner():
+    """plan(C, P, graphs) -> (vec, lpc, cpb, threads, ncb, psplit, grid) of film_fwd for fp32 features on dense
+    16-byte aligned tensors, straight from mrp_film_mean_fwd_plan (made-up pointers: it makes no GPU call)."""
+    import ctypes
+    from mrp_gnn_amd import _lib
+    lib = _lib.load_library()
+    plan = _lib.AggPlan()
+    ref = ctypes.byref(plan)
+    a = ctypes.c_void_p(1 << 20)
+
+    def run(C, P, g):
+        code = lib.mrp_film_mean_fwd_plan(0, a, C * P, a, a, a, a, a, g.num_graphs, g.max_nodes, g.graph_kind,
+                                          g.num_nodes, g.num_edges, C, P, 0, a, C * P, None, ref)
+        assert code == 0 and plan.kernel_name == "film_fwd"
+        return plan.vec, plan.lpc, plan.cpb, plan.threads, plan.ncb, plan.psplit, plan.grid
+    return lib, run
+
+
+def test_make_geometry_mirror_is_the_planner():
+    """``geometry_cases.make_geometry`` against what the plan query reports for film_fwd — the same
+    ``make_geometry(C, P, vec, tu.fwd_lo, tu.fwd_hi, tu.fwd_cap)`` call the two launchers make — for fp32 CSR graphs
+    with ``fwd_vec2_below`` 0, at every shape of ``FWD_ROWS``: fwd_cap over its whole range against each of fwd_lo
+    and fwd_hi over its whole range (the other at its ends and in between: ``lo_hi_pairs``), and the whole
+    fwd_lo x fwd_hi product at the default cap."""
+    assert RANGES["fwd_lo"] == RANGES["fwd_hi"] == (1, 256) and RANGES["fwd_cap"] == (1, 16)
+    shapes = sorted({(r.C, r.H * r.W, max(r.ns)) for r in gc.FWD_ROWS})
+    graphs_ = {n: gc.graph_ns("csr", (n, max(n - 1, 1))) for _, _, n in shapes}
+    lib, plan = _film_fwd_planner()
+    settings = [(lo, hi, cap) for lo, hi in lo_hi_pairs() for cap in range(1, 17)]
+    settings += [(lo, hi, 16) for lo in range(1, 257) for hi in range(1, 257)]
+    try:
+        assert lib.mrp_tuning_set(b"reset", 0) == 0 and lib.mrp_tuning_set(b"fwd_vec2_below", 0) == 0
+        for lo, hi, cap in settings:
+            assert lib.mrp_tuning_set(b"fwd_lo", lo) == lib.mrp_tuning_set(b"fwd_hi", hi) == \
+                lib.mrp_tuning_set(b"fwd_cap", cap) == 0
+            for C, P, n in shapes:
+                vec = 4 if P % 4 == 0 else 1
+                lpc, cpb, threads, ncb = gc.make_geometry(C, P, vec, lo, hi, cap)
+                want = (vec, lpc, cpb, threads, ncb, 1, 2 * ncb)
+                assert plan(C, P, graphs_[n]) == want, (lo, hi, cap, C, P, n)
+    finally:
+        assert lib.mrp_tuning_set(b"reset", 0) == 0
+
+
+@pytest.mark.parametrize("row", gc.FWD_ROWS, ids=[r.name for r in gc.FWD_ROWS])
+def test_forward_row_names_the_geometry_its_knobs_reach(row):
+    assert set(row.knobs) <= {"fwd_lo", "fwd_hi", "fwd_cap"} and row.knobs and len(row.ns) == 2
+    kn = {k[4:]: v for k, v in row.knobs.items()}
+    assert tuple(row.geo) == gc.forward_geometry(row, **kn), gc.forward_geometry(row, **kn)
+    assert tuple(row.geo) != gc.forward_geometry(row), "the row's knobs change nothing"
+    vec, lpc, cpb, psplit = row.geo
+    assert (row.H * row.W) % vec == 0 and cpb * lpc <= gc.KBLOCK
+    assert row.C % cpb or cpb == 1  # the last channel block is ragged
+    if row.kind == "complete":
+        assert len(set(row.ns)) == 1
+    else:
+        assert row.ns[1] < row.ns[0] and psplit == 1
+
+
+@pytest.mark.parametrize("family", ["max", "wmean"])
+def test_forward_rows_cover_what_they_must(family):
+    rows = [r for r in gc.FWD_ROWS if r.family == family]
+    assert len(rows) >= 12
+    assert {r.geo[1] for r in rows} >= {1, 2, 4, 64, 128, 256}
+    assert any(r.geo[1] == 256 and (r.H, r.W, r.key) == (32, 32, "f32") for r in rows)
+    assert {r.knobs.get("fwd_cap") for r in rows} >= {1, 3, 16}
+    assert any(r.C % r.geo[2] for r in rows if "fwd_cap" in r.knobs)
+    assert any(r.knobs.get("fwd_lo", 0) > r.knobs.get("fwd_hi", 256) for r in rows)
+    assert any((r.knobs.get("fwd_lo"), r.knobs.get("fwd_hi")) == (3, 100) for r in rows)
+    assert {4 if max(r.ns) <= 4 else 8 if max(r.ns) <= 8 else 16 for r in rows} == {4, 8, 16}  # "max_bucket"
+    # a complete graph's plane split with a ragged last segment; CSR and k-NN rows whose lanes walk several slices
+    assert any(r.kind == "complete" and r.geo[3] > 1 and (r.H * r.W // r.geo[0]) % r.geo[1] for r in rows)
+    for kind in ("csr", "knn4"):
+        assert any(r.kind == kind and r.H * r.W // r.geo[0] >= 2 * r.geo[1] for r in rows)
+    assert any(r.geo[0] == 1 and (r.H, r.W) == (5, 5) for r in rows)
+    assert {r.key for r in rows} == {"f32", "bf16", "f16"}
+    if family == "wmean":
+        assert {r.mode for r in rows} == {"mean", "sum"}
+        assert any(r.w_odd and r.geo[0] == 1 and (r.H * r.W) % 4 == 0 for r in rows)
+    else:
+        assert any(r.geo[0] == 8 for r in rows)
 
 
 # ------------------------------------------------------------------- the GEMMs' workgroup -> tile order

@@ -12,6 +12,11 @@ output whose per-element arithmetic does not depend on the geometry must have th
 the forward and grad_x of the VALU kernels, where a lane computes its elements alone, in source order — but not
 grad_gb, whose reduction tree follows the lanes per plane — and every GEMM output, since the tile order changes
 which workgroup computes a tile, not the tile.
+
+``film_max_fwd`` and ``film_wmean_fwd`` take film_fwd's ``fwd_lo`` / ``fwd_hi`` / ``fwd_cap`` and have no plan query:
+``geometry_cases.FWD_ROWS`` names by hand the geometry each row's knobs reach, test_geometry_cpu.py holds that to a
+mirror of the planner (itself held to the plan query), and ``test_forward_row_under_knobs`` runs each row under its
+knobs and under the defaults: bit-identical, the default run under the family's own bar.
 """
 import functools
 
@@ -22,11 +27,14 @@ import mrp_gnn_amd as m
 from mrp_gnn_amd import aggregate, compress
 import geometry_cases as gc
 import half_cases as hc
+import max_cases as mc
 import oracle
 import test_gpu_compress_cl as t_half_cl
 import test_gpu_compress_gemm as t_split
 import test_gpu_compress_half as t_half
 import test_gpu_compress_split_cl as t_split_cl
+import test_gpu_film_wmean as t_wmean
+import wmean_cases as wmc
 from conftest import rel_err
 from test_gpu_properties import TOL
 
@@ -162,6 +170,78 @@ def test_row_against_float64(cuda_device, name):
         assert torch.equal(hc.bits(out), hc.bits(dout)), (name, "forward bits depend on the geometry")
     if plans["bwd"].kernel_name == dplans["bwd"].kernel_name and plans["bwd"].kernel_name in VALU:
         assert torch.equal(hc.bits(dx), hc.bits(ddx)), (name, "grad_x bits depend on the geometry")
+
+
+# ------------------------------------------------- film_max_fwd and film_wmean_fwd under film_fwd's knobs
+@functools.lru_cache(maxsize=None)
+def fwd_case(name):
+    """CPU inputs of a ``geometry_cases.FWD_ROWS`` row and its reference: film_max on the 2^-3 lattice (every
+    message exact in every dtype: ``max_cases.reference`` in fp32 is the exact result), film_wmean on random
+    operands with ``wmean_cases``' weights against ``wmean_cases.forward`` in float64."""
+    row = next(r for r in gc.FWD_ROWS if r.name == name)
+    T = gc.DTYPES[row.key]
+    g = graph(row.kind, row.ns)
+    seed = sum(map(ord, name)) * 977
+    if row.family == "max":
+        x, gb, _, _ = mc.lattice_operands(g, row.C, row.H, row.W, seed)
+        return row, x.to(T), gb, None, mc.reference(g, x, gb)[0]
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(g.num_nodes(), row.C, row.H, row.W, generator=gen).to(T)
+    gb = torch.sigmoid(torch.randn(g.num_edges(), row.C, 2, generator=gen))
+    w = wmc.weights_of(g.num_nodes(), row.H, row.W, gen)
+    return row, x, gb, w, wmc.forward(g, x.double(), gb.double(), w.double(), row.mode)
+
+
+def fwd_run(row, dev, knobs_, w_odd):
+    """The row's forward under the given knobs.  w_odd: w as rows of a (N, P + 1) buffer, a node stride that is no
+    multiple of 4 elements."""
+    _, x, gb, w, _ = fwd_case(row.name)
+    csr = csr_of(row, dev)
+    xd, gbd = x.to(dev), gb.to(dev)
+    assert xd.data_ptr() % 16 == 0 and xd.is_contiguous()  # what ``forward_geometry`` assumes
+    out = torch.empty_like(xd)
+    key = "%s_fwd_%s" % (row.family, row.key)
+    before = aggregate.PATH_COUNTS[key]
+    with gc.knobs(**knobs_):
+        if row.family == "max":
+            aggregate.film_max_forward_into(xd, gbd, csr, 0, out)
+        else:
+            n, P = w.shape[0], row.H * row.W
+            wd = w.to(dev)
+            if w_odd:
+                buf = torch.zeros(n, P + 1, device=dev)
+                buf[:, :P] = wd.view(n, P)
+                wd = buf.as_strided((n, row.H, row.W), (P + 1, row.W, 1))
+                assert P % 4 == 0 and wd.stride(0) % 4 and wd.data_ptr() % 16 == 0
+            aggregate.film_wmean_forward_into(xd, gbd, wd, csr, 0, out, row.mode)
+        torch.cuda.synchronize()
+    assert aggregate.PATH_COUNTS[key] == before + 1
+    return out.cpu()
+
+
+@pytest.mark.parametrize("name", [r.name for r in gc.FWD_ROWS])
+def test_forward_row_under_knobs(cuda_device, name):
+    """film_max_fwd / film_wmean_fwd at the geometry the row's knobs select (test_geometry_cpu.py holds the row's
+    hand-written geometry to the planner's mirror) against the default-knob run: bit-identical — a lane computes its
+    pixels alone, the row's sources in source order, whatever the lanes per plane, the channels per workgroup and
+    the plane split — and the default-knob run under the family's own bar against its reference."""
+    row, x, gb, w, ref = fwd_case(name)
+    T = gc.DTYPES[row.key]
+    knobbed = fwd_run(row, cuda_device, row.knobs, row.w_odd)
+    default = fwd_run(row, cuda_device, {}, row.w_odd)
+    assert knobbed.dtype == default.dtype == T
+    assert torch.equal(hc.bits(knobbed), hc.bits(default)), (name, "forward bits depend on the geometry")
+    if row.family == "max":
+        assert torch.equal(hc.bits(default), hc.bits(ref.to(T))), name
+    elif row.key == "f32":
+        e = rel_err(default.numpy(), ref.numpy())
+        print(name, "rel_err", e)
+        assert e <= t_wmean.TOL, (name, e)
+    else:
+        hc.assert_elementwise(default, ref, T, name)
+    if row.w_odd:  # single elements because of w alone: "the per-element sums do not depend on slice width"
+        aligned = fwd_run(row, cuda_device, {}, False)
+        assert torch.equal(hc.bits(aligned), hc.bits(default)), (name, "forward bits depend on the slice width")
 
 
 # ----------------------------------------------------------------------------- the GEMMs' tile order

@@ -16,7 +16,19 @@ gradient, aggregation forward, ``grad_x``) the output bits equal the same entry 
 the operands; a declined call wrote nothing; and in both cases no byte outside the permitted blocks was
 touched and the inputs hold their bits (``Arena.check``).  The Python routes (``compress.py``,
 ``aggregate.py``) must return correct values for the same sparse views — a ``RuntimeError`` for a legal
-tensor is a failure."""
+tensor is a failure.
+
+One aggregation case, ``complete_1x16_s512``, is a single 16-node graph with nodes ``2^29 bytes + 64 KiB`` apart: it
+spans 2^32 bytes by itself, which no graph of the others does.  The mean's matrix-core backward cannot address
+that (32-bit lane offsets over a graph's nodes) and its launcher must run the VALU kernels instead: grad_x and
+grad_gb are held to the bits of the dense run with the matrix-core knobs off, and grad_gb must differ from the dense
+default-knob run's.
+
+The max-pooled, attention-pooled, confidence-weighted and confidence-gated aggregations
+(``mrp_film_{max,attn,wmean,wattn}_{fwd,bwd}``) run on all seven graph sets of ``span_cases.AGG`` with x, out,
+grad_out, grad_x, grad_x_base, w and grad_w sparse: every output, the dense fp32 ones included, has the bits of
+the dense run, and the dense run is held to the family's own reference under the family's own bar
+(``_fam_bars``)."""
 import ctypes
 import functools
 
@@ -26,11 +38,19 @@ import torch
 
 import mrp_gnn_amd as m
 from mrp_gnn_amd import _lib, aggregate, compress
+import attn_cases as ac
 import half_cases as hc
+import max_cases as mc
 import oracle
 import span_cases as sp
 import split_cases as sc
 import stack_ref
+import test_gpu_film_attn as t_attn
+import test_gpu_film_max as t_max
+import test_gpu_film_wattn as t_wattn
+import test_gpu_film_wmean as t_wmean
+import wattn_cases as wac
+import wmean_cases as wmc
 from conftest import rel_err
 from test_gpu_parity import TOL
 from test_gpu_split_fp32 import FACTOR
@@ -412,12 +432,15 @@ def test_compress_python_node_ranges(arena, key, monkeypatch):
 # ---- aggregation ----------------------------------------------------------------------------------------
 MODES = {"film_mean": _lib.MODE_FILM_MEAN, "film_sum": _lib.MODE_FILM_SUM, "copy_mean": _lib.MODE_COPY_MEAN}
 #: (case, mode): all three modes on the first graph set
-AGG_RUNS = [("complete_3x8", mo) for mo in MODES] + [(ca, "film_mean") for ca in list(sp.AGG)[1:]]
-AGG_CL_RUNS = [(ca, "film_mean") for ca in sp.AGG_CL]
+AGG_RUNS = [("complete_3x8", mo) for mo in MODES] + \
+    [(ca, "film_mean") for ca in sp.AGG_S[1:] + ("complete_1x16_s512",)]
+AGG_CL_RUNS = [(ca, "film_mean") for ca in sp.AGG_CL_SPAN]
 #: cases whose backward is given a grad_x base (the first half of a concatenation's gradient)
 WITH_BASE = ("complete_3x8", "ragged_8_5_1_8")
 #: 9..16-node graphs with whole 64-pixel planes: the matrix-core backward
 MFMA_CASES = ("complete_2x12", "knn4_2x12")
+#: the 16-node graph whose own nodes lie more than 2^32 bytes apart: the matrix-core backward must step aside
+SELF_SPAN = "complete_1x16_s512"
 
 
 @functools.lru_cache(maxsize=None)
@@ -430,7 +453,8 @@ def _agraph(case):
     else:
         gs = [m.frame_graph(hc._poses(rng, k), knn=knn) for k in sizes]
     g = m.batch(gs)
-    assert g.num_nodes() == sum(sizes) >= 18
+    assert g.num_nodes() == sum(sizes)
+    assert (sum(sizes) - 1) * sp.agg_stride(case, 2) >= 1 << 32  # the last node lies beyond 2^32 bytes
     return g
 
 
@@ -522,8 +546,7 @@ def _run_aggregation(arena, key, case, mode, layout):
     ref = _aref(case, key, mode)
     gbd = gb.to(dev)
     csr, graph = _graph(case, dev, gbd, C, P, mode)
-    stride = sp.NODE_STRIDE + extra * x.element_size()
-    kw = dict(layout=layout, ps=2 * C if layout == "cl" else None, stride_bytes=stride)
+    kw = dict(layout=layout, ps=2 * C if layout == "cl" else None, stride_bytes=sp.agg_stride(case, x.element_size()))
     fwd, bwd = ("mrp_film_mean_fwd_t", "mrp_film_mean_bwd_t") if layout == "nchw" else \
         ("mrp_film_mean_fwd_cl", "mrp_film_mean_bwd_cl")
     what = f"{layout} {key} {case} {mode}"
@@ -561,7 +584,9 @@ def _run_aggregation(arena, key, case, mode, layout):
     dgb2 = torch.empty_like(dgb)
     assert _agg_bwd(lib, key, layout, case, mode, _dense_in(Gc, dev, layout), _dense_in(x, dev, layout), graph, dDX,
                     _dense_in(base, dev, layout) if with_base else None, dgb2, st) == 0
-    _same_bits(dx, dDX.read(), what + " grad_x")
+    self_span = layout == "nchw" and case == SELF_SPAN
+    if not self_span:  # (there the dense run is another kernel's, whose grad_x is a matrix-core product: below)
+        _same_bits(dx, dDX.read(), what + " grad_x")
     if layout == "nchw" and case in MFMA_CASES:
         # The matrix-core backward's launcher checks 15 node strides + two planes against 2^32 and, if they do
         # not fit, quietly runs film_bwd_dx + the Gram pass instead.  15 S fits, so the matrix-core kernel must
@@ -574,6 +599,21 @@ def _run_aggregation(arena, key, case, mode, layout):
                             _dense_out(shape, T, dev, layout), None, dgb3, st) == 0
         _dgb_bar(dgb3.cpu(), ref, key, mode, what + " grad_gb, VALU kernels")
         assert not torch.equal(dgb3, dgb2), what + ": the knobs did not change the kernel"
+    if self_span:
+        # The mirror image: 15 node strides of 2^29 bytes + 64 KiB do not fit the matrix-core backward's 32-bit
+        # lane offsets, so the launcher must have kept film_bwd_dx + the Gram pass: grad_x and grad_gb have the
+        # bits of the dense run with the matrix-core kernels switched off, and grad_gb not those of the dense
+        # default-knob run (whose strides fit, and which therefore ran the matrix-core kernel).
+        dgb3 = torch.empty_like(dgb)
+        dDX3 = _dense_out(shape, T, dev, layout)
+        with sc.knobs(compress.compress_path(), bwd_complete_mfma=0, bwd_regular_mfma=0):
+            assert _agg_bwd(lib, key, layout, case, mode, _dense_in(Gc, dev, layout), _dense_in(x, dev, layout), graph,
+                            dDX3, None, dgb3, st) == 0
+        _same_bits(dx, dDX3.read(), what + " grad_x, VALU kernels")
+        _agg_bar(dDX.read(), want, key, what + " grad_x, dense matrix-core run")
+        _same_bits(dgb, dgb3, what + " grad_gb, VALU kernels")
+        _dgb_bar(dgb2.cpu(), ref, key, mode, what + " grad_gb, dense matrix-core run")
+        assert not torch.equal(dgb, dgb2), what + ": the matrix-core kernel ran on strides its lane offsets cannot hold"
 
 
 @pytest.mark.parametrize("case,mode", AGG_RUNS, ids=lambda v: str(v))
@@ -582,7 +622,8 @@ def test_aggregation_node_major(arena, key, case, mode):
     """``mrp_film_mean_fwd_t`` / ``_bwd_t``: 64-bit per-graph bases, 32-bit per-lane byte offsets.  3 x 8 nodes:
     the fused backward, 16-byte slices, the cat epilogue; 2 x 12: the matrix-core backward (its lane offsets
     hold up to 15 node strides); k-NN(4); ragged CSR with a node without in-edges and a grad_x base; P = 15
-    with an odd node stride: one element per access."""
+    with an odd node stride: one element per access; one 16-node graph 2^29 bytes + 64 KiB a node: a graph that
+    spans 2^32 bytes by itself, where the matrix-core backward must leave the call to the VALU kernels."""
     _run_aggregation(arena, key, case, mode, "nchw")
 
 
@@ -596,7 +637,7 @@ def test_aggregation_pixel_major(arena, key, case, mode):
 
 #: (layout, case, mode): every C-ABI case of either layout, and all three modes on the first graph set of both
 AGG_PY_RUNS = [("nchw", ca, mo) for ca, mo in AGG_RUNS] + \
-    [("cl", "complete_3x8", mo) for mo in MODES] + [("cl", ca, "film_mean") for ca in sp.AGG_CL[1:]]
+    [("cl", "complete_3x8", mo) for mo in MODES] + [("cl", ca, "film_mean") for ca in sp.AGG_CL_SPAN[1:]]
 
 
 @pytest.mark.parametrize("layout,case,mode", AGG_PY_RUNS, ids=lambda v: str(v))
@@ -614,7 +655,7 @@ def test_aggregation_python_routes(arena, key, layout, case, mode):
     gbd = gb.to(dev) if mode != "copy_mean" else None
     csr = _agraph(case).csr(dev)
     kw = dict(layout=layout, ps=2 * C if layout == "cl" else None,
-              stride_bytes=sp.NODE_STRIDE + extra * x.element_size())
+              stride_bytes=sp.agg_stride(case, x.element_size()))
     what = f"python {layout} {key} {case} {mode}"
     X = arena.place(x, **kw)
     XC = arena.reserve(x.shape, T, **kw)
@@ -639,8 +680,310 @@ def test_aggregation_python_routes(arena, key, layout, case, mode):
     dOUT = _dense_out(x.shape, T, dev, layout).t
     aggregate.film_mean_forward_into(dX, gbd, csr, MODES[mode], dOUT)
     _same_bits(out, dOUT, what + " out")
-    dxd, _ = aggregate.film_mean_backward(dG, dX, gbd, csr, MODES[mode], True, True, grad_x_base=dB)
+    # the self-spanning graph: the sparse views do not fit the matrix-core backward's lane offsets, so they ran
+    # film_bwd_dx + the Gram pass — the dense operands' kernels only with the matrix-core ones switched off
+    valu = dict(bwd_complete_mfma=0, bwd_regular_mfma=0) if (layout, case) == ("nchw", SELF_SPAN) else {}
+    with sc.knobs(compress.compress_path(), **valu):
+        dxd, dgbd = aggregate.film_mean_backward(dG, dX, gbd, csr, MODES[mode], True, True, grad_x_base=dB)
     _same_bits(dx, dxd, what + " grad_x")
+    if valu:
+        _same_bits(dgb, dgbd, what + " grad_gb")
+
+
+# ---- the max-pooled, attention-pooled, confidence-weighted and confidence-gated aggregations -----------------
+FAMILIES = ("max", "attn", "wmean", "wattn")
+FAM_TOL = {"max": t_max.TOL, "attn": t_attn.TOL, "wmean": t_wmean.TOL, "wattn": t_wattn.TOL}
+#: the outputs of each family: out, grad_x (features, node-strided), grad_w (fp32, node-strided), the rest dense fp32
+FAM_OUTS = {"max": ("out", "dx", "dgb"), "attn": ("out", "attn", "dx", "dgb"), "wmean": ("out", "dx", "dgb", "dw"),
+            "wattn": ("out", "attn", "rate", "dx", "dgb", "dw")}
+WIDE = "wide_3x8_c17_p80"
+#: (family, case, film_wmean's mode): every graph set; film_wmean in both modes on the first
+FAM_RUNS = [(fam, ca, "mean") for fam in FAMILIES for ca in sp.AGG_FAMILIES] + [("wmean", "complete_3x8", "sum")]
+FAM_PY_RUNS = [(fam, ca) for fam in FAMILIES for ca in ("complete_3x8", "ragged_8_5_1_8", WIDE)]
+
+
+def _fam_base(case):
+    return case in WITH_BASE or case == WIDE
+
+
+@functools.lru_cache(maxsize=None)
+def _fops(fam, case, key):
+    """CPU operands of a family on a graph set: x, G, base in T (drawn in fp32, rounded once), gb fp32 gamma / beta,
+    w fp32 sender maps (None for the families without them).  film_max: ``max_cases.lattice_operands``, whose values
+    every dtype holds exactly; film_wattn: without loud senders; film_wmean: ``wmean_cases``' weights."""
+    _, _, C, H, W, _ = sp.AGG[case]
+    g = _agraph(case)
+    n, E = g.num_nodes(), g.num_edges()
+    seed = sum(map(ord, case + fam)) * 131
+    w = None
+    if fam == "max":
+        x, gb, G, base = mc.lattice_operands(g, C, H, W, seed)
+    elif fam == "attn":
+        x, gb, _, G, base = ac.random_operands(g, C, H, W, seed)
+    elif fam == "wattn":
+        x, gb, _, G, base, w, louds = wac.random_operands(g, C, H, W, seed, loud=False)
+        assert louds == ()
+    else:
+        gen = torch.Generator().manual_seed(seed)
+        x, G, base = (torch.randn(n, C, H, W, generator=gen) for _ in range(3))
+        gb = torch.sigmoid(torch.randn(E, C, 2, generator=gen))
+        w = wmc.weights_of(n, H, W, gen)
+    T = sp.DTYPES[key]
+    return dict(x=x.to(T), G=G.to(T), base=base.to(T), gb=gb, w=w)
+
+
+@functools.lru_cache(maxsize=None)
+def _fref(fam, case, key, mode):
+    """The family's own reference on the widened operands: name -> float64 tensor (film_max: fp32, exact on the
+    lattice; film_wmean: also name + "32", the fp32 restatement ``stack_ref.within`` measures against)."""
+    o = _fops(fam, case, key)
+    g = _agraph(case)
+    x, G = o["x"].float(), o["G"].float()
+    base = o["base"].float() if _fam_base(case) else None
+    if fam == "max":
+        return dict(zip(FAM_OUTS[fam], mc.reference(g, x, o["gb"], G, base=base)))
+    if fam == "attn":
+        return dict(zip(FAM_OUTS[fam], ac.reference(g, x, o["gb"], G, base=base, dtype=torch.float64)))
+    if fam == "wattn":
+        return dict(zip(FAM_OUTS[fam], wac.reference(g, x, o["gb"], o["w"], G, base=base, dtype=torch.float64)))
+    ref = {}
+    for tag, dt in (("", torch.float64), ("32", torch.float32)):
+        out, dx, dgb, dw = wmc.backward(g, x.to(dt), o["gb"].to(dt), o["w"].to(dt), G.to(dt), mode=mode)
+        ref.update({"out" + tag: out, "dx" + tag: dx + (base.to(dt) if base is not None else 0), "dgb" + tag: dgb,
+                    "dw" + tag: dw})
+    return ref
+
+
+def _fam_fwd(lib, fam, key, case, mode, csr, gbd, X, Wt, OUT, st):
+    """The family's forward entry point on operands with ``ptr`` / ``ns``: (code, attn, rate); attn and rate are
+    dense (E, P) fp32 tensors (the ABI gives them no stride), NaN-filled before the call."""
+    _, _, C, H, W, _ = sp.AGG[case]
+    P, dev, dt = H * W, gbd.device, sp.ENUM[key]
+    ga = aggregate._graph_args(gbd, csr, C, P, 0)
+    attn = rate = None
+    if fam in ("attn", "wattn"):
+        attn = torch.full((csr.num_edges, P), float("nan"), device=dev)
+        scale = ac.default_scale(C)
+    if fam == "max":
+        code = lib.mrp_film_max_fwd(dt, X.ptr, X.ns, *ga, OUT.ptr, OUT.ns, st)
+    elif fam == "attn":
+        assert lib.mrp_film_attn_workspace(0, *ga[5:12]) == 0
+        code = lib.mrp_film_attn_fwd(dt, X.ptr, X.ns, *ga, OUT.ptr, OUT.ns, scale, _p(attn), None, 0, st)
+    elif fam == "wmean":
+        code = lib.mrp_film_wmean_fwd(dt, X.ptr, X.ns, ga[0], Wt.ptr, Wt.ns, *ga[1:], aggregate.WAGG_MODES[mode],
+                                      OUT.ptr, OUT.ns, st)
+    else:
+        assert lib.mrp_film_wattn_workspace(0, *ga[5:12]) == 0
+        rate = torch.full((csr.num_edges, P), float("nan"), device=dev)
+        code = lib.mrp_film_wattn_fwd(dt, X.ptr, X.ns, ga[0], Wt.ptr, Wt.ns, *ga[1:], OUT.ptr, OUT.ns, scale, _p(attn),
+                                      _p(rate), None, 0, st)
+    torch.cuda.synchronize(dev)
+    return code, attn, rate
+
+
+def _fam_bwd(lib, fam, key, case, mode, csr, gbd, G, X, Wt, DX, B, DW, attn, rate, st):
+    """The family's backward entry point with the workspace its query asks for: (code, grad_gb).  On the wide
+    case the attention families' per-tile grad_gb partials (P = 80: two tiles) and film_wmean's per-block grad_w
+    partials (C = 17: two blocks) go through that workspace."""
+    _, _, C, H, W, _ = sp.AGG[case]
+    P, dev, dt = H * W, gbd.device, sp.ENUM[key]
+    ga = aggregate._graph_args(gbd, csr, C, P, 0)
+    dgb = torch.full((csr.num_edges, C, 2), float("nan"), device=dev)
+    head = (dt, G.ptr, G.ns, X.ptr, X.ns)
+    tail = (DX.ptr, DX.ns) + ((B.ptr, B.ns) if B is not None else (None, 0)) + (_p(dgb),)
+    if fam == "max":
+        code = lib.mrp_film_max_bwd(*head, *ga, *tail, st)
+    else:
+        query = {"attn": lambda: lib.mrp_film_attn_workspace(1, *ga[5:12]),
+                 "wattn": lambda: lib.mrp_film_wattn_workspace(1, *ga[5:12]),
+                 "wmean": lambda: lib.mrp_film_wmean_workspace(*ga[5:12])}[fam]
+        nbytes = int(query())
+        assert nbytes >= 0 and (nbytes > 0 or case != WIDE), (fam, case, nbytes)
+        ws = torch.full(((nbytes + 3) // 4,), float("nan"), device=dev) if nbytes > 0 else None
+        if fam == "attn":
+            code = lib.mrp_film_attn_bwd(*head, *ga, *tail, ac.default_scale(C), _p(attn), _p(ws), nbytes, st)
+        elif fam == "wmean":
+            code = lib.mrp_film_wmean_bwd(*head, ga[0], Wt.ptr, Wt.ns, *ga[1:], aggregate.WAGG_MODES[mode], *tail,
+                                          DW.ptr, DW.ns, _p(ws), nbytes, st)
+        else:
+            code = lib.mrp_film_wattn_bwd(*head, ga[0], Wt.ptr, Wt.ns, *ga[1:], *tail, ac.default_scale(C), _p(attn),
+                                          _p(rate), DW.ptr, DW.ns, _p(ws), nbytes, st)
+    torch.cuda.synchronize(dev)
+    return code, dgb
+
+
+def _fam_dense_of(lib, st, fam, key, case, mode, dev, o, T):
+    """Forward and backward of the family's entry points in ``key`` (elements of T) on dense copies of the operands
+    ``o``, widened exactly where T is wider than they are: name -> CPU tensor."""
+    x, Gc, base = (o[k].to(T) for k in ("x", "G", "base"))
+    n, C, H, W = x.shape
+    csr, gbd = _agraph(case).csr(dev), o["gb"].to(dev)
+    X, G = _dense_in(x, dev, "nchw"), _dense_in(Gc, dev, "nchw")
+    B = _dense_in(base, dev, "nchw") if _fam_base(case) else None
+    Wt = _dense_in(o["w"].view(n, 1, H, W), dev, "nchw") if o["w"] is not None else None
+    OUT, DX = (_dense_out((n, C, H, W), T, dev, "nchw") for _ in range(2))
+    DW = _dense_out((n, 1, H, W), torch.float32, dev, "nchw") if Wt is not None else None
+    code, attn, rate = _fam_fwd(lib, fam, key, case, mode, csr, gbd, X, Wt, OUT, st)
+    assert code == 0, (fam, key, case, code)
+    code, dgb = _fam_bwd(lib, fam, key, case, mode, csr, gbd, G, X, Wt, DX, B, DW, attn, rate, st)
+    assert code == 0, (fam, key, case, code)
+    res = dict(out=OUT.read(), dx=DX.read(), dgb=dgb.cpu())
+    for name, t in (("attn", attn), ("rate", rate)):
+        if t is not None:
+            res[name] = t.cpu()
+    if DW is not None:
+        res["dw"] = DW.read()
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def _fam_bars(fam, key, case, mode, dev):
+    """The dense run of the entry points in ``key``, held to the family's own bar against its own reference; the
+    sparse runs are then compared with it bit for bit.  Computed once per (family, dtype, case, mode).
+
+    The fp32 kernels (on the operands widened exactly): film_max bit for bit with ``max_cases.reference`` (lattice
+    operands: every message and sum is exact, no near-tie can be routed differently); film_attn and film_wattn every
+    output within ``TOL`` of the float64 reference (``test_against_float64``); film_wmean out and grad_x within
+    ``TOL``, grad_gb and grad_w under ``stack_ref.within`` (``test_g3_random_maps_against_float64``).  16-bit features
+    as each family's own 16-bit contract test holds them: the fp32 kernels' outputs on the widened input, out and
+    grad_x cast once, the fp32 outputs bit for bit; film_wmean (whose header promises that of the forward alone):
+    the forward so, and out, grad_x, grad_gb, grad_w under the bars of ``test_g3``."""
+    lib, st = m.load_library(), _st(dev)
+    o = _fops(fam, case, key)
+    ref = _fref(fam, case, key, mode)
+    what = f"dense {fam} {key} {case} {mode}"
+    r32 = _fam_dense_of(lib, st, fam, "f32", case, mode, dev, o, torch.float32)
+    for name in FAM_OUTS[fam]:
+        got = r32[name].reshape(ref[name].shape)
+        if fam == "max":
+            _same_bits(got, ref[name], f"{what} {name} against the reference")
+        elif fam == "wmean" and name in ("dgb", "dw"):
+            ok, errs = stack_ref.within(got, ref[name + "32"], ref[name])
+            print(what, name, "err, fp32 torch err", errs)
+            assert ok, (what, name, errs)
+        else:
+            e = rel_err(got.numpy(), ref[name].numpy())
+            print(what, name, "rel_err", e)
+            assert e <= FAM_TOL[fam], (what, name, e)
+    if key == "f32":
+        return r32
+    T = sp.DTYPES[key]
+    rT = _fam_dense_of(lib, st, fam, key, case, mode, dev, o, T)
+    for name in FAM_OUTS[fam]:
+        assert rT[name].dtype == (T if name in ("out", "dx") else torch.float32), (what, name)
+        if fam != "wmean" or name == "out":
+            _same_bits(rT[name], r32[name].to(rT[name].dtype), f"{what} {name} against the fp32 kernels', cast once")
+        if fam == "wmean" and name in ("out", "dx"):
+            hc.assert_elementwise(rT[name], ref[name], T, f"{what} {name}")
+        elif fam == "wmean":
+            ok, errs = stack_ref.within(rT[name].reshape(ref[name].shape), ref[name + "32"], ref[name])
+            assert ok, (what, name, errs)
+    return rT
+
+
+def _fam_place(arena, fam, key, case):
+    """x, grad_out, grad_x_base and w sparse in the arena, each in a slot of its own (the outputs are reserved by
+    the caller).  w (n, 1, H, W) fp32 at the case's stride in its own element size."""
+    o = _fops(fam, case, key)
+    n, C, H, W = o["x"].shape
+    kw = dict(stride_bytes=sp.agg_stride(case, o["x"].element_size()))
+    kw32 = dict(stride_bytes=sp.agg_stride(case, 4))
+    X = arena.place(o["x"], **kw)
+    G = arena.place(o["G"], **kw)
+    B = arena.place(o["base"], **kw) if _fam_base(case) else None
+    Wt = arena.place(o["w"].view(n, 1, H, W), **kw32) if o["w"] is not None else None
+    return X, G, B, Wt, kw, kw32
+
+
+@pytest.mark.parametrize("fam,case,mode", FAM_RUNS, ids=lambda v: str(v))
+@pytest.mark.parametrize("key", ALL)
+def test_family_node_major(arena, key, fam, case, mode):
+    """``mrp_film_{max,attn,wmean,wattn}_{fwd,bwd}`` with x, out, grad_out, grad_x, grad_x_base, w and grad_w sparse
+    in the arena (gb, attn, rate, grad_gb and the workspaces dense: the ABI gives them no stride): the return code
+    of the table, ``Arena.check``, and every output — grad_gb, attn, rate and grad_w included — with the bits of
+    the dense run, which ``_fam_bars`` holds to the family's own reference.
+
+    Why the bits cannot depend on the strides.  Every kernel is deterministic (no atomics, one writer per element).
+    film_max, film_wmean: a lane computes its own elements, the sources of a row in row order; grad_gb is summed
+    per lane over its slices, then by a fixed butterfly over the plane's lanes, and film_wmean's grad_w over
+    channels in blocks of 16 — orders fixed by C, P, the graph and the slice width, and the slice width is the same
+    in both runs (every stride here is a multiple of 16 bytes but the P = 15 case's, where both runs take single
+    elements).  film_attn, film_wattn: every access is one element and the order of every sum is a function of C, P
+    and the graph alone (the header says so)."""
+    dev = arena.dev
+    lib, st = m.load_library(), _st(dev)
+    dense = _fam_bars(fam, key, case, mode, dev)
+    o = _fops(fam, case, key)
+    n, C, H, W = o["x"].shape
+    T = sp.DTYPES[key]
+    csr, gbd = _agraph(case).csr(dev), o["gb"].to(dev)
+    e_fwd, e_bwd = sp.FAMILY_ENTRIES[fam]
+    what = f"{fam} {key} {case} {mode}"
+    X, G, B, Wt, kw, kw32 = _fam_place(arena, fam, key, case)
+    ins = [p for p in (X, G, B, Wt) if p is not None]
+    OUT = arena.reserve((n, C, H, W), T, **kw)
+    code, attn, rate = _fam_fwd(lib, fam, key, case, mode, csr, gbd, X, Wt, OUT, st)
+    assert code == sp.expected(e_fwd, key, case), (what, code)
+    (out,) = arena.check(ins, [OUT])
+    _same_bits(out, dense["out"], what + " out")
+    for name, t in (("attn", attn), ("rate", rate)):
+        if t is not None:
+            _same_bits(t, dense[name], f"{what} {name}")
+    DX = arena.reserve((n, C, H, W), T, **kw)
+    DW = arena.reserve((n, 1, H, W), torch.float32, **kw32) if Wt is not None else None
+    code, dgb = _fam_bwd(lib, fam, key, case, mode, csr, gbd, G, X, Wt, DX, B, DW, attn, rate, st)
+    assert code == sp.expected(e_bwd, key, case), (what, code)
+    got = arena.check(ins, [DX] + ([DW] if DW is not None else []))
+    _same_bits(got[0], dense["dx"], what + " grad_x")
+    _same_bits(dgb, dense["dgb"], what + " grad_gb")
+    if DW is not None:
+        _same_bits(got[1], dense["dw"], what + " grad_w")
+
+
+@pytest.mark.parametrize("fam,case", FAM_PY_RUNS, ids=lambda v: str(v))
+@pytest.mark.parametrize("key", ALL)
+def test_family_python_routes(arena, key, fam, case):
+    """``aggregate.film_*_forward_into`` on sparse x and w views into a sparse out, and ``film_*_backward`` on sparse
+    grad_out / x / grad_x_base / w views (its outputs are its own dense tensors): the dense run's bits, one forward
+    and one backward of the family's own dtype key, and nothing else moved."""
+    dev = arena.dev
+    dense = _fam_bars(fam, key, case, "mean", dev)
+    o = _fops(fam, case, key)
+    n, C, H, W = o["x"].shape
+    T = sp.DTYPES[key]
+    csr, gbd = _agraph(case).csr(dev), o["gb"].to(dev)
+    what = f"python {fam} {key} {case}"
+    X, G, B, Wt, kw, _ = _fam_place(arena, fam, key, case)
+    ins = [p for p in (X, G, B, Wt) if p is not None]
+    OUT = arena.reserve((n, C, H, W), T, **kw)
+    before = dict(aggregate.PATH_COUNTS)
+    attn = rate = None
+    if fam == "max":
+        aggregate.film_max_forward_into(X.view(), gbd, csr, 0, OUT.view())
+    elif fam == "attn":
+        attn = aggregate.film_attn_forward_into(X.view(), gbd, csr, 0, OUT.view())
+    elif fam == "wmean":
+        aggregate.film_wmean_forward_into(X.view(), gbd, Wt.view(), csr, 0, OUT.view())
+    else:
+        attn, rate = aggregate.film_wattn_forward_into(X.view(), gbd, Wt.view(), csr, 0, OUT.view(), rate=True)
+    (out,) = arena.check(ins, [OUT])
+    dw = None
+    if fam == "max":
+        dx, dgb = aggregate.film_max_backward(G.view(), X.view(), gbd, csr, 0, True, True, grad_x_base=B.view())
+    elif fam == "attn":
+        dx, dgb = aggregate.film_attn_backward(G.view(), X.view(), gbd, attn, csr, 0, True, True, grad_x_base=B.view())
+    elif fam == "wmean":
+        dx, dgb, dw = aggregate.film_wmean_backward(G.view(), X.view(), gbd, Wt.view(), csr, 0, True, True, True,
+                                                    grad_x_base=B.view())
+    else:
+        dx, dgb, dw = aggregate.film_wattn_backward(G.view(), X.view(), gbd, Wt.view(), attn, rate, csr, 0, True, True,
+                                                    True, grad_x_base=B.view())
+    arena.check(ins, [])
+    moved = {k: v - before.get(k, 0) for k, v in aggregate.PATH_COUNTS.items() if v != before.get(k, 0)}
+    assert moved == {f"{fam}_fwd_{key}": 1, f"{fam}_bwd_{key}": 1}, (what, moved)
+    got = dict(out=out, attn=attn, rate=rate, dx=dx, dgb=dgb, dw=dw)
+    for name in FAM_OUTS[fam]:
+        _same_bits(got[name].reshape(dense[name].shape), dense[name], f"{what} {name}")
 
 
 # ---- encoder: row strides ---------------------------------------------------------------------------------

@@ -30,7 +30,11 @@ def rows(g):
 def weights(name, seed=0):
     """(N, H, W) fp32 sender maps of a half_cases case (see the module docstring)."""
     n, _, H, W = hc.shape(name)
-    gen = torch.Generator().manual_seed(sum(map(ord, name)) * 977 + 13 + seed)
+    return weights_of(n, H, W, torch.Generator().manual_seed(sum(map(ord, name)) * 977 + 13 + seed))
+
+
+def weights_of(n, H, W, gen):
+    """(n, H, W) fp32 sender maps drawn from ``gen`` (see the module docstring)."""
     w = 1.0 / 16 + (1.0 - 1.0 / 16) * torch.rand(n, H, W, generator=gen)
     w.view(-1)[torch.randperm(w.numel(), generator=gen)[:w.numel() // 4]] = 0.0  # a quarter: exact zeros
     flat = w.view(n, -1)

@@ -767,6 +767,117 @@ int64_t mrp_film_wattn_workspace(int32_t direction, int32_t num_graphs, int32_t 
                                  int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P);
 
 /*
+ * Multi-head attention fusion (ABI 22, extended): mrp_film_attn_* and mrp_film_wattn_* with `heads` = H
+ * independent channel groups, so that different channel groups can listen to different robots at the same
+ * pixel.  Ch = C / H; head k owns channels [k Ch, (k+1) Ch).  The signatures are the single-head ones with
+ * `int32_t heads` after `C, P, flags` (after `C, P` in the workspace queries); every other entry point is
+ * unchanged.
+ *
+ * Per-head formulas: for every head k, m_j, s_j, a_j, out, da, ds, dm, grad_x and grad_gb are
+ * mrp_film_attn_*'s formulas with "sum over c" meaning the head's Ch channels, ascending; for the gated form
+ * mx, t_j, Z, r_j and dbar follow the same rule.  One `scale` serves all heads (the customary value is
+ * 1 / sqrt(Ch)).
+ *
+ * Outputs: attn, and rate for the gated form, are (H, E, P) fp32, head-major: attn + k E P is exactly the
+ * (E, P) array of a single-head call.  out, grad_x and grad_gb keep their shapes.
+ *
+ * Confidence maps: w (num_nodes, P) is shared by all heads (a sender's map says where it transmits, not which
+ * channels).  grad_w[u,p] is the sum over heads, ascending, of the single-head grad_w chain of that head:
+ * head 0's value first, then one fp32 add per further head.  No atomics, one writer per element (every head
+ * writes a partial (H, num_nodes, P) in the workspace and a reduce pass adds them in head order).
+ *
+ * Bit-level contract, for every graph kind, flag, dtype, node stride and base: head k of the H-head call equals
+ * mrp_film_attn_fwd / _bwd (or mrp_film_wattn_*) called with C = Ch; x, out, grad_out, grad_x and grad_x_base
+ * offset by k Ch P elements with the same node strides; a contiguous copy of gb[:, k Ch : (k+1) Ch, :]; and
+ * attn + k E P, rate + k E P — bit for bit in out, attn, rate, grad_x and grad_gb[:, k Ch : (k+1) Ch, :];
+ * grad_w equals the ordered head sum above.  (Chunk boundaries of the channel sweeps count from the head's
+ * first channel.)  The order of every sum is a function of Ch, P and the graph only.  The 16-bit contract
+ * carries over unchanged: fwd(T, x) == T(fwd(float(x))), and attn, rate, grad_gb, grad_w are equal in fp32.
+ * heads = 1 runs the single-head kernels: the bits of mrp_film_attn_* / mrp_film_wattn_*.
+ *
+ * Non-finite values: the containment tightens.  A NaN or infinity at (node, channel c, pixel p) reaches only
+ * the channels of c's head at p in out and grad_x, and only attn + k E P and rate + k E P of that head
+ * (grad_gb: the columns of that head; grad_w sums over heads, so its element at (node, p) may be affected).
+ *
+ * Validation precedes any launch: everything the single-head entry points reject is rejected, and
+ * hipErrorInvalidValue is also returned for heads < 1, for C > 0 with C % heads != 0 and for heads > 65535.
+ * Empty work returns success, with attn, rate (all heads), grad_gb and grad_w, where given, written as zeros.
+ * For non-COMPLETE graphs the hipMemsetAsync of attn, rate and grad_gb covers all heads.
+ *
+ * Workspace: with heads = 1 both queries return the single-head queries' values.  mrp_film_attn_workspace_mh is
+ * mrp_film_attn_workspace's value for every H (the per-tile grad_gb partials [tile][E][C][2] hold every head's
+ * columns).  mrp_film_wattn_workspace_mh(direction != 0) adds heads * num_nodes * P * 4 bytes when heads > 1:
+ * grad_w's per-head partials, placed after the grad_gb partials that the call needs (at the start where
+ * grad_gb is not wanted or a plane is one tile); that space is needed only where grad_w is wanted.
+ *
+ * Large operands: every typed pointer is offset in 64-bit arithmetic (k Ch P, k E P and k num_nodes P are formed
+ * in int64_t), so the spans may exceed 2^31 elements as for the single-head entry points: x, out, grad_out,
+ * grad_x and grad_x_base span (num_nodes - 1) * stride + C * P elements, attn and rate H * E * P floats.
+ */
+int mrp_film_attn_fwd_mh(int32_t dtype,
+                         const void* x, int64_t x_node_stride,
+                         const float* gb,
+                         const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                         const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                         int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                         int32_t C, int32_t P, int32_t flags, int32_t heads,
+                         void* out, int64_t out_node_stride,
+                         float scale, float* attn,
+                         void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+int mrp_film_attn_bwd_mh(int32_t dtype,
+                         const void* grad_out, int64_t g_node_stride,
+                         const void* x, int64_t x_node_stride,
+                         const float* gb,
+                         const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                         const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                         int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                         int32_t C, int32_t P, int32_t flags, int32_t heads,
+                         void* grad_x, int64_t gx_node_stride,
+                         const void* grad_x_base, int64_t base_node_stride,
+                         float* grad_gb,
+                         float scale, const float* attn,
+                         void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+int64_t mrp_film_attn_workspace_mh(int32_t direction, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                   int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t heads);
+
+int mrp_film_wattn_fwd_mh(int32_t dtype,
+                          const void* x, int64_t x_node_stride,
+                          const float* gb,
+                          const float* w, int64_t w_node_stride,
+                          const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                          const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                          int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                          int32_t C, int32_t P, int32_t flags, int32_t heads,
+                          void* out, int64_t out_node_stride,
+                          float scale, float* attn, float* rate,
+                          void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+int mrp_film_wattn_bwd_mh(int32_t dtype,
+                          const void* grad_out, int64_t g_node_stride,
+                          const void* x, int64_t x_node_stride,
+                          const float* gb,
+                          const float* w, int64_t w_node_stride,
+                          const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                          const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                          int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                          int32_t C, int32_t P, int32_t flags, int32_t heads,
+                          void* grad_x, int64_t gx_node_stride,
+                          const void* grad_x_base, int64_t base_node_stride,
+                          float* grad_gb,
+                          float scale, const float* attn, const float* rate,
+                          float* grad_w, int64_t gw_node_stride,
+                          void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+int64_t mrp_film_wattn_workspace_mh(int32_t direction, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
+                                    int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t heads);
+
+/*
  * The layer's 1x1 compress convolution and its gradients, fp32 on the matrix cores (exact fp32
  * products, v_mfma_f32_32x32x2_f32), without the concatenation (dgl/model/models.py:163-165,181-184,
  * 186-189: h = conv(torch.cat((x, a), 1)) with conv = nn.Conv2d(2C, C, kernel_size=1)).  W is the

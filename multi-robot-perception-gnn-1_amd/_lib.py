@@ -42,6 +42,12 @@ EXPORTED_SYMBOLS = (
     "mrp_film_wattn_fwd",
     "mrp_film_wattn_bwd",
     "mrp_film_wattn_workspace",
+    "mrp_film_attn_fwd_mh",
+    "mrp_film_attn_bwd_mh",
+    "mrp_film_attn_workspace_mh",
+    "mrp_film_wattn_fwd_mh",
+    "mrp_film_wattn_bwd_mh",
+    "mrp_film_wattn_workspace_mh",
     "mrp_film_wmean_fwd",
     "mrp_film_wmean_bwd",
     "mrp_film_wmean_workspace",
@@ -230,6 +236,17 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.mrp_film_wattn_bwd.restype = ctypes.c_int
     lib.mrp_film_wattn_workspace.argtypes = [_I32] * 8
     lib.mrp_film_wattn_workspace.restype = ctypes.c_int64
+    # the multi-head forms: `heads` follows `C, P, flags` (`C, P` in the workspace queries)
+    wf, wb = lib.mrp_film_wattn_fwd.argtypes, lib.mrp_film_wattn_bwd.argtypes
+    for name, args, at in (("mrp_film_attn_fwd_mh", fa, 16), ("mrp_film_attn_bwd_mh", ba, 18),
+                           ("mrp_film_wattn_fwd_mh", wf, 18), ("mrp_film_wattn_bwd_mh", wb, 20)):
+        fn = getattr(lib, name)
+        fn.argtypes = args[:at] + [_I32] + args[at:]
+        fn.restype = ctypes.c_int
+    lib.mrp_film_attn_workspace_mh.argtypes = [_I32] * 9
+    lib.mrp_film_attn_workspace_mh.restype = ctypes.c_int64
+    lib.mrp_film_wattn_workspace_mh.argtypes = [_I32] * 9
+    lib.mrp_film_wattn_workspace_mh.restype = ctypes.c_int64
     # the confidence-weighted aggregation: (w, w_node_stride) follow gb, wagg follows flags; the backward
     # ends with grad_w, gw_node_stride, workspace, workspace_bytes, stream
     lib.mrp_film_wmean_fwd.argtypes = [_I32, _P, _I64, _P, _P, _I64] + graph[:-1] + [_I32, _I32, _P, _I64, _P]

@@ -971,6 +971,10 @@ def film_max_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Ten
 # edge id, rows no CSR entry names zero; the backward reads them back and recomputes only the messages.
 # Every CSR entry is its own message (parallel edges, self-loops); every in-degree must be
 # <= ``_lib.FILM_ATTN_DEGREE``.  channels_last features take the copy-first route, as for the max.
+#
+# ``heads=H`` > 1 (``mrp_film_attn_fwd_mh`` / ``_bwd_mh``): head k owns channels [k C/H, (k+1) C/H) and has its
+# own scores and softmax — bit for bit the single-head operator on that channel slice — in one launch whose
+# grid is H times larger; the weights are (H, E, H*W) head-major and scale defaults to 1 / sqrt(C / H).
 # ---------------------------------------------------------------------------------------------------------
 def _check_attn_degree(csr: GraphCSR) -> None:
     bound = getattr(csr, "max_in_degree", -1)
@@ -1006,6 +1010,20 @@ def _attn_scale(scale, C: int) -> float:
     return s
 
 
+def _check_heads(heads, C: int) -> int:
+    """The head count of a multi-head call: a positive int that divides C."""
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"film_attn heads must be a positive int, got {heads!r}")
+    if C % heads:
+        raise ValueError(f"film_attn heads must divide the channels: C = {C}, heads = {heads}")
+    return heads
+
+
+def _weights_shape(csr: GraphCSR, P: int, heads: int):
+    """(E, P) of a single-head call, (H, E, P) head-major of a multi-head one."""
+    return (csr.num_edges, P) if heads == 1 else (heads, csr.num_edges, P)
+
+
 def _attn_workspace(lib, direction: int, csr: GraphCSR, C: int, P: int, device):
     nbytes = lib.mrp_film_attn_workspace(direction, csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes,
                                          csr.num_edges, C, P)
@@ -1015,17 +1033,20 @@ def _attn_workspace(lib, direction: int, csr: GraphCSR, C: int, P: int, device):
 
 
 def film_attn_forward_into(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, flags: int, out: torch.Tensor,
-                           scale: Optional[float] = None, attn: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           scale: Optional[float] = None, attn: Optional[torch.Tensor] = None,
+                           heads: int = 1) -> torch.Tensor:
     """Run ``mrp_film_attn_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
     half of a ``torch.cat((h, g_h), 1)`` buffer — and return the weights ``attn`` (E, H*W) fp32 (written
-    into the given tensor, else a new one).  ``flags``: 0 or ``_lib.GB_LOGITS``.  No autograd."""
+    into the given tensor, else a new one).  ``flags``: 0 or ``_lib.GB_LOGITS``.  ``heads`` > 1 runs
+    ``mrp_film_attn_fwd_mh``: attn is then (heads, E, H*W).  No autograd."""
     _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
     _require_device(x, out, attn)
     flags = _check_attn_flags(flags)
     if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
         raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
     n, C, H, W = x.shape
-    scale = _attn_scale(scale, C)
+    heads = _check_heads(heads, C)
+    scale = _attn_scale(scale, C // heads)
     x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
     os_ = node_stride(out)
     if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
@@ -1033,33 +1054,40 @@ def film_attn_forward_into(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, fla
     if n != csr.num_nodes:
         raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
     gb = _attn_gb(gb, csr, C)
+    wshape = _weights_shape(csr, H * W, heads)
     if attn is None:
-        attn = torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
-    elif tuple(attn.shape) != (csr.num_edges, H * W) or attn.dtype != torch.float32 or not attn.is_contiguous():
-        raise ValueError(f"attn must be a contiguous {(csr.num_edges, H * W)} float32 tensor")
+        attn = torch.empty(wshape, device=x.device, dtype=torch.float32)
+    elif tuple(attn.shape) != wshape or attn.dtype != torch.float32 or not attn.is_contiguous():
+        raise ValueError(f"attn must be a contiguous {wshape} float32 tensor")
     lib = _lib.load_library()
     with torch.cuda.device(x.device):
         ws, nbytes = _attn_workspace(lib, 0, csr, C, H * W, x.device)
-        code = lib.mrp_film_attn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *_graph_args(gb, csr, C, H * W, flags),
-                                     _ptr(out), os_, scale, _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
-    _lib.check(code, "mrp_film_attn_fwd")
-    PATH_COUNTS["attn_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+        ga = _graph_args(gb, csr, C, H * W, flags)
+        if heads == 1:
+            code = lib.mrp_film_attn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *ga, _ptr(out), os_, scale,
+                                         _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
+        else:
+            code = lib.mrp_film_attn_fwd_mh(FEATURE_DTYPES[x.dtype], _ptr(x), xs, *ga, heads, _ptr(out), os_, scale,
+                                            _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
+    _lib.check(code, "mrp_film_attn_fwd" if heads == 1 else "mrp_film_attn_fwd_mh")
+    PATH_COUNTS[("attn_fwd_" if heads == 1 else "attn_fwd_mh_") + _DTYPE_KEYS[x.dtype]] += 1
     return attn
 
 
 def film_attn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, attn: torch.Tensor, csr: GraphCSR,
                        flags: int, need_dx: bool, need_dgb: bool, grad_x_base: Optional[torch.Tensor] = None,
-                       scale: Optional[float] = None):
+                       scale: Optional[float] = None, heads: int = 1):
     """(grad_x or None, grad_gb (E, C, 2) or None) of :func:`film_attn_forward_into`, ``attn`` being the
-    weights it returned; ``grad_x_base`` (N, C, H, W), if given, is added into grad_x by the kernel.  grad_x is
-    NCHW in x's dtype, grad_gb fp32 with every unnamed row zero."""
+    weights it returned (``heads`` as there); ``grad_x_base`` (N, C, H, W), if given, is added into grad_x by
+    the kernel.  grad_x is NCHW in x's dtype, grad_gb fp32 with every unnamed row zero."""
     _check_attn_degree(csr)
     _require_device(grad_out, x, attn)
     flags = _check_attn_flags(flags)
     if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
         raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
     n, C, H, W = x.shape
-    scale = _attn_scale(scale, C)
+    heads = _check_heads(heads, C)
+    scale = _attn_scale(scale, C // heads)
     if n != csr.num_nodes:
         raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
     # the kernel reads grad_out, the base and attn with x's extents: a mismatch would be an out-of-bounds read
@@ -1067,8 +1095,9 @@ def film_attn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor
         raise ValueError(f"grad_out must be {(n, C, H, W)}, got {tuple(grad_out.shape)}")
     if grad_x_base is not None and tuple(grad_x_base.shape) != (n, C, H, W):
         raise ValueError(f"grad_x_base must be {(n, C, H, W)}, got {tuple(grad_x_base.shape)}")
-    if tuple(attn.shape) != (csr.num_edges, H * W) or attn.dtype != torch.float32:
-        raise ValueError(f"attn must be {(csr.num_edges, H * W)} float32, got {tuple(attn.shape)} {attn.dtype}")
+    wshape = _weights_shape(csr, H * W, heads)
+    if tuple(attn.shape) != wshape or attn.dtype != torch.float32:
+        raise ValueError(f"attn must be {wshape} float32, got {tuple(attn.shape)} {attn.dtype}")
     if grad_x_base is not None:
         _require_device(grad_x_base)
     attn = attn.contiguous()
@@ -1092,12 +1121,15 @@ def film_attn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor
     lib = _lib.load_library()
     with torch.cuda.device(x.device):
         ws, nbytes = _attn_workspace(lib, 1, csr, C, H * W, x.device) if need_dgb else (None, 0)
-        code = lib.mrp_film_attn_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs,
-                                     *_graph_args(gb, csr, C, H * W, flags), _ptr(dx),
-                                     (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb),
-                                     scale, _ptr(attn), _ptr(ws), nbytes, _stream(x.device))
-    _lib.check(code, "mrp_film_attn_bwd")
-    PATH_COUNTS["attn_bwd_" + _DTYPE_KEYS[dtype]] += 1
+        ga = _graph_args(gb, csr, C, H * W, flags)
+        tail = (_ptr(dx), (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb), scale, _ptr(attn),
+                _ptr(ws), nbytes, _stream(x.device))
+        if heads == 1:
+            code = lib.mrp_film_attn_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, *ga, *tail)
+        else:
+            code = lib.mrp_film_attn_bwd_mh(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, *ga, heads, *tail)
+    _lib.check(code, "mrp_film_attn_bwd" if heads == 1 else "mrp_film_attn_bwd_mh")
+    PATH_COUNTS[("attn_bwd_" if heads == 1 else "attn_bwd_mh_") + _DTYPE_KEYS[dtype]] += 1
     return dx, dgb
 
 
@@ -1107,11 +1139,11 @@ class FilmAttnFunction(torch.autograd.Function):
     ``_lib.GB_LOGITS`` (gb = pre-sigmoid logits; the gradient is then d logits)."""
 
     @staticmethod
-    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale):
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale, heads: int = 1):
         out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
-        attn = film_attn_forward_into(x, gb, csr, flags, out, scale)
+        attn = film_attn_forward_into(x, gb, csr, flags, out, scale, heads=heads)
         ctx.save_for_backward(x, gb, attn)
-        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.csr, ctx.flags, ctx.scale, ctx.heads = csr, flags, scale, heads
         ctx.mark_non_differentiable(attn)
         return out, attn
 
@@ -1119,14 +1151,14 @@ class FilmAttnFunction(torch.autograd.Function):
     def backward(ctx, grad_out, _grad_attn):
         x, gb, attn = ctx.saved_tensors
         dx, dgb = film_attn_backward(grad_out, x, gb, attn, ctx.csr, ctx.flags, ctx.needs_input_grad[0],
-                                     ctx.needs_input_grad[1], scale=ctx.scale)
+                                     ctx.needs_input_grad[1], scale=ctx.scale, heads=ctx.heads)
         if dgb is not None:
             dgb = dgb.view(gb.shape).to(gb.dtype)
-        return dx, dgb, None, None, None
+        return dx, dgb, None, None, None, None
 
 
 def film_attn(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
-              scale: Optional[float] = None, return_weights: bool = False):
+              scale: Optional[float] = None, return_weights: bool = False, heads: int = 1):
     """Per-location attention over the FiLM messages of each destination's in-neighbours: at every pixel the
     receiver's feature vector scores each message ``gamma_e * x_src + beta_e`` (``scale`` times their dot
     product over the channels, ``1/sqrt(C)`` by default), a softmax over the node's in-edges turns the scores
@@ -1138,10 +1170,15 @@ def film_attn(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = F
     gamma/beta, or their pre-sigmoid logits with ``logits=True``; csr: ``RobotGraph.csr(device)``, every
     in-degree <= ``_lib.FILM_ATTN_DEGREE`` (``ValueError`` otherwise).  A self-loop lets a node attend to
     itself.  With ``return_weights=True`` returns ``(out, attn)``, attn (E, H*W) fp32 by edge id — the
-    weights saved for the backward, not differentiable."""
+    weights saved for the backward, not differentiable.
+
+    ``heads=H`` > 1 is multi-head attention in one launch: head k owns channels [k C/H, (k+1) C/H) with its own
+    scores and softmax (exactly ``film_attn`` on that channel slice), ``scale`` defaults to ``1/sqrt(C/H)``
+    and attn is (H, E, H*W).  ``ValueError`` unless H is a positive int dividing C."""
     _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    heads = _check_heads(heads, x.shape[1] if x.dim() == 4 else 0)  # host-side too
     _check_x(x)
-    out, attn = FilmAttnFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale)
+    out, attn = FilmAttnFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale, heads)
     return (out, attn) if return_weights else out
 
 
@@ -1151,13 +1188,13 @@ class FilmAttnCatFunction(torch.autograd.Function):
     the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
 
     @staticmethod
-    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale):
+    def forward(ctx, x, gb, csr: GraphCSR, flags: int, scale, heads: int = 1):
         n, C, H, W = x.shape
         buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
-        attn = film_attn_forward_into(x, gb, csr, flags, buf[:, C:], scale)
+        attn = film_attn_forward_into(x, gb, csr, flags, buf[:, C:], scale, heads=heads)
         buf[:, :C].copy_(x)
         ctx.save_for_backward(x, gb, attn)
-        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.csr, ctx.flags, ctx.scale, ctx.heads = csr, flags, scale, heads
         ctx.mark_non_differentiable(attn)
         return buf, attn
 
@@ -1168,32 +1205,33 @@ class FilmAttnCatFunction(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0]
         dx, dgb = film_attn_backward(grad_buf[:, C:], x, gb, attn, ctx.csr, ctx.flags, need_dx,
                                      ctx.needs_input_grad[1], grad_x_base=grad_buf[:, :C] if need_dx else None,
-                                     scale=ctx.scale)
+                                     scale=ctx.scale, heads=ctx.heads)
         if dgb is not None:
             dgb = dgb.view(gb.shape).to(gb.dtype)
-        return dx, dgb, None, None, None
+        return dx, dgb, None, None, None, None
 
 
 def film_attn_cat(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
-                  scale: Optional[float] = None, return_weights: bool = False):
-    """``torch.cat((x, film_attn(x, gb, csr, logits, scale)), dim=1)`` without a concatenation pass for the
-    aggregate."""
+                  scale: Optional[float] = None, return_weights: bool = False, heads: int = 1):
+    """``torch.cat((x, film_attn(x, gb, csr, logits, scale, heads=heads)), dim=1)`` without a concatenation pass
+    for the aggregate."""
     _check_attn_degree(csr)
+    heads = _check_heads(heads, x.shape[1] if x.dim() == 4 else 0)  # host-side too
     _check_x(x)
-    buf, attn = FilmAttnCatFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale)
+    buf, attn = FilmAttnCatFunction.apply(x, gb, csr, _lib.GB_LOGITS if logits else 0, scale, heads)
     return (buf, attn) if return_weights else buf
 
 
 def film_attn_residual(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, logits: bool = False,
-                       scale: Optional[float] = None) -> torch.Tensor:
+                       scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
     """``x + film_attn(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
-    return x + film_attn(x, gb, csr, logits, scale)
+    return x + film_attn(x, gb, csr, logits, scale, heads=heads)
 
 
 def film_attn_mix(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, x0: torch.Tensor, alpha: float,
-                  logits: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+                  logits: bool = False, scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
     """``(1 - alpha) * film_attn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
-    return (1.0 - float(alpha)) * film_attn(x, gb, csr, logits, scale) + float(alpha) * x0
+    return (1.0 - float(alpha)) * film_attn(x, gb, csr, logits, scale, heads=heads) + float(alpha) * x0
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1436,19 +1474,20 @@ def film_wmean_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: Grap
 # ---------------------------------------------------------------------------------------------------------
 def film_wattn_forward_into(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, flags: int,
                             out: torch.Tensor, scale: Optional[float] = None, attn: Optional[torch.Tensor] = None,
-                            rate=False):
+                            rate=False, heads: int = 1):
     """Run ``mrp_film_wattn_fwd`` into ``out`` (N, C, H, W) — which may be a strided view such as the second
     half of a ``torch.cat((h, g_h), 1)`` buffer — and return ``(attn, rate)``: the weights (E, H*W) fp32
     (written into the given tensor, else a new one) and, with ``rate=True`` or a tensor to write into, the
-    rates (E, H*W) fp32 the backward needs for grad_w (else None).  ``flags``: 0 or ``_lib.GB_LOGITS``.  No
-    autograd."""
+    rates (E, H*W) fp32 the backward needs for grad_w (else None).  ``flags``: 0 or ``_lib.GB_LOGITS``.
+    ``heads`` > 1 runs ``mrp_film_wattn_fwd_mh``: attn and rate are then (heads, E, H*W).  No autograd."""
     _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
     _require_device(x, out, attn, rate if isinstance(rate, torch.Tensor) else None)
     flags = _check_attn_flags(flags)
     if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
         raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
     n, C, H, W = x.shape
-    scale = _attn_scale(scale, C)
+    heads = _check_heads(heads, C)
+    scale = _attn_scale(scale, C // heads)
     x, xs = _as_node_major(x)  # a channels_last x is copied to NCHW here
     os_ = node_stride(out)
     if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
@@ -1457,32 +1496,38 @@ def film_wattn_forward_into(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, 
         raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
     w, wst = _wmean_weights(w, n, H, W)
     gb = _attn_gb(gb, csr, C)
+    wshape = _weights_shape(csr, H * W, heads)
     bufs = []
     for name, t in (("attn", attn), ("rate", rate)):
         if t is None or t is False:
-            t = None if name == "rate" else torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
+            t = None if name == "rate" else torch.empty(wshape, device=x.device, dtype=torch.float32)
         elif t is True:
-            t = torch.empty((csr.num_edges, H * W), device=x.device, dtype=torch.float32)
-        elif tuple(t.shape) != (csr.num_edges, H * W) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {(csr.num_edges, H * W)} float32 tensor")
+            t = torch.empty(wshape, device=x.device, dtype=torch.float32)
+        elif tuple(t.shape) != wshape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {wshape} float32 tensor")
         bufs.append(t)
     attn, rate = bufs
     lib = _lib.load_library()
     ga = _graph_args(gb, csr, C, H * W, flags)
     with torch.cuda.device(x.device):
-        code = lib.mrp_film_wattn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, ga[0], _ptr(w), wst, *ga[1:], _ptr(out),
-                                      os_, scale, _ptr(attn), _ptr(rate), None, 0, _stream(x.device))
-    _lib.check(code, "mrp_film_wattn_fwd")
-    PATH_COUNTS["wattn_fwd_" + _DTYPE_KEYS[x.dtype]] += 1
+        tail = (_ptr(out), os_, scale, _ptr(attn), _ptr(rate), None, 0, _stream(x.device))
+        if heads == 1:
+            code = lib.mrp_film_wattn_fwd(FEATURE_DTYPES[x.dtype], _ptr(x), xs, ga[0], _ptr(w), wst, *ga[1:], *tail)
+        else:
+            code = lib.mrp_film_wattn_fwd_mh(FEATURE_DTYPES[x.dtype], _ptr(x), xs, ga[0], _ptr(w), wst, *ga[1:], heads,
+                                             *tail)
+    _lib.check(code, "mrp_film_wattn_fwd" if heads == 1 else "mrp_film_wattn_fwd_mh")
+    PATH_COUNTS[("wattn_fwd_" if heads == 1 else "wattn_fwd_mh_") + _DTYPE_KEYS[x.dtype]] += 1
     return attn, rate
 
 
 def film_wattn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor,
                         attn: torch.Tensor, rate: Optional[torch.Tensor], csr: GraphCSR, flags: int, need_dx: bool,
                         need_dgb: bool, need_dw: bool, grad_x_base: Optional[torch.Tensor] = None,
-                        scale: Optional[float] = None):
+                        scale: Optional[float] = None, heads: int = 1):
     """(grad_x, grad_gb (E, C, 2), grad_w (N, H, W)) of :func:`film_wattn_forward_into`, each None unless asked
-    for; ``attn`` and ``rate`` are what it returned (``rate`` is needed for grad_w only); ``grad_x_base``
+    for; ``attn`` and ``rate`` are what it returned, ``heads`` as there (``rate`` is needed for grad_w only;
+    with several heads grad_w is the sum over the heads, ascending); ``grad_x_base``
     (N, C, H, W), if given, is added into grad_x by the kernel.  grad_x is NCHW in x's dtype, grad_gb and grad_w
     are fp32."""
     _check_attn_degree(csr)
@@ -1491,7 +1536,9 @@ def film_wattn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tenso
     if x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
         raise ValueError("node features must be (N, C, H, W) float32, bfloat16 or float16")
     n, C, H, W = x.shape
-    scale = _attn_scale(scale, C)
+    heads = _check_heads(heads, C)
+    scale = _attn_scale(scale, C // heads)
+    wshape = _weights_shape(csr, H * W, heads)
     if n != csr.num_nodes:
         raise ValueError(f"x has {n} nodes, graph has {csr.num_nodes}")
     # the kernel reads grad_out, the base, attn and rate with x's extents: a mismatch would be an out-of-bounds read
@@ -1504,8 +1551,8 @@ def film_wattn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tenso
             if need_dw:
                 raise ValueError("grad_w needs the forward's rate (film_wattn_forward_into(..., rate=True))")
             continue
-        if tuple(t.shape) != (csr.num_edges, H * W) or t.dtype != torch.float32:
-            raise ValueError(f"{name} must be {(csr.num_edges, H * W)} float32, got {tuple(t.shape)} {t.dtype}")
+        if tuple(t.shape) != wshape or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be {wshape} float32, got {tuple(t.shape)} {t.dtype}")
     if grad_x_base is not None:
         _require_device(grad_x_base)
     w, wst = _wmean_weights(w, n, H, W)
@@ -1532,18 +1579,18 @@ def film_wattn_backward(grad_out: torch.Tensor, x: torch.Tensor, gb: torch.Tenso
     ga = _graph_args(gb, csr, C, H * W, flags)
     lib = _lib.load_library()
     work, nbytes = None, 0
-    if need_dgb:
-        nbytes = lib.mrp_film_wattn_workspace(1, csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes,
-                                              csr.num_edges, C, H * W)
+    if need_dgb or (need_dw and heads > 1):  # the tiles' grad_gb partials, the heads' grad_w partials
+        sizes = (1, csr.num_graphs, csr.max_nodes, csr.graph_kind, csr.num_nodes, csr.num_edges, C, H * W)
+        nbytes = lib.mrp_film_wattn_workspace(*sizes) if heads == 1 else lib.mrp_film_wattn_workspace_mh(*sizes, heads)
         if nbytes > 0:
             work = torch.empty(((nbytes + 3) // 4,), device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
-        code = lib.mrp_film_wattn_bwd(FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, ga[0], _ptr(w), wst,
-                                      *ga[1:], _ptr(dx), (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs,
-                                      _ptr(dgb), scale, _ptr(attn), _ptr(rate), _ptr(dw),
-                                      H * W if dw is not None else 0, _ptr(work), nbytes, _stream(x.device))
-    _lib.check(code, "mrp_film_wattn_bwd")
-    PATH_COUNTS["wattn_bwd_" + _DTYPE_KEYS[dtype]] += 1
+        tail = (_ptr(dx), (C * H * W) if dx is not None else 0, _ptr(grad_x_base), bs, _ptr(dgb), scale, _ptr(attn),
+                _ptr(rate), _ptr(dw), H * W if dw is not None else 0, _ptr(work), nbytes, _stream(x.device))
+        head = (FEATURE_DTYPES[dtype], _ptr(grad_out), gs, _ptr(x), xs, ga[0], _ptr(w), wst, *ga[1:])
+        code = lib.mrp_film_wattn_bwd(*head, *tail) if heads == 1 else lib.mrp_film_wattn_bwd_mh(*head, heads, *tail)
+    _lib.check(code, "mrp_film_wattn_bwd" if heads == 1 else "mrp_film_wattn_bwd_mh")
+    PATH_COUNTS[("wattn_bwd_" if heads == 1 else "wattn_bwd_mh_") + _DTYPE_KEYS[dtype]] += 1
     return dx, dgb, dw
 
 
@@ -1551,12 +1598,12 @@ def _wattn_grads(ctx, grad_out, base):
     x, gb, w, attn, rate = ctx.saved_tensors
     need = ctx.needs_input_grad
     dx, dgb, dw = film_wattn_backward(grad_out, x, gb, w, attn, rate, ctx.csr, ctx.flags, need[0], need[1], need[2],
-                                      grad_x_base=base if need[0] else None, scale=ctx.scale)
+                                      grad_x_base=base if need[0] else None, scale=ctx.scale, heads=ctx.heads)
     if dgb is not None:
         dgb = dgb.view(gb.shape).to(gb.dtype)
     if dw is not None:
         dw = dw.view(w.shape)
-    return dx, dgb, dw, None, None, None
+    return dx, dgb, dw, None, None, None, None
 
 
 class FilmWAttnFunction(torch.autograd.Function):
@@ -1565,11 +1612,12 @@ class FilmWAttnFunction(torch.autograd.Function):
     computed and saved only when w requires a gradient.  ``flags`` may be ``_lib.GB_LOGITS``."""
 
     @staticmethod
-    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale):
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale, heads: int = 1):
         out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
-        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, out, scale, rate=ctx.needs_input_grad[2])
+        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, out, scale, rate=ctx.needs_input_grad[2],
+                                             heads=heads)
         ctx.save_for_backward(x, gb, w, attn, rate)
-        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.csr, ctx.flags, ctx.scale, ctx.heads = csr, flags, scale, heads
         ctx.mark_non_differentiable(attn)
         return out, attn
 
@@ -1579,7 +1627,7 @@ class FilmWAttnFunction(torch.autograd.Function):
 
 
 def film_wattn(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
-               scale: Optional[float] = None, return_weights: bool = False):
+               scale: Optional[float] = None, return_weights: bool = False, heads: int = 1):
     """:func:`film_attn` over what was delivered: at every pixel the receiver attends over the in-neighbours
     whose map ``w`` is positive there, each softmax term weighted by the sender's confidence
     (``a_j ~ w[src e_j] exp(s_j)``); pixels nobody delivered to give 0, and a silent sender's features reach
@@ -1590,10 +1638,12 @@ def film_wattn(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR
     their pre-sigmoid logits with ``logits=True``; w: (N, H, W) or (N, 1, H, W) fp32 >= 0, each node's plane
     contiguous — the sender's map, indexed by source node; csr: ``RobotGraph.csr(device)``, every in-degree <=
     ``_lib.FILM_ATTN_DEGREE``.  With ``return_weights=True`` returns ``(out, attn)``, attn (E, H*W) fp32 by edge
-    id, not differentiable."""
+    id, not differentiable.  ``heads=H`` > 1: as for :func:`film_attn`; the maps w are shared by the heads and
+    w's gradient sums over them."""
     _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    heads = _check_heads(heads, x.shape[1] if x.dim() == 4 else 0)  # host-side too
     _check_x(x)
-    out, attn = FilmWAttnFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale)
+    out, attn = FilmWAttnFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale, heads)
     return (out, attn) if return_weights else out
 
 
@@ -1603,13 +1653,14 @@ class FilmWAttnCatFunction(torch.autograd.Function):
     the kernel the second half of the incoming gradient as grad_out and the first half as grad_x's base."""
 
     @staticmethod
-    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale):
+    def forward(ctx, x, gb, w, csr: GraphCSR, flags: int, scale, heads: int = 1):
         n, C, H, W = x.shape
         buf = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
-        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, buf[:, C:], scale, rate=ctx.needs_input_grad[2])
+        attn, rate = film_wattn_forward_into(x, gb, w, csr, flags, buf[:, C:], scale, rate=ctx.needs_input_grad[2],
+                                             heads=heads)
         buf[:, :C].copy_(x)
         ctx.save_for_backward(x, gb, w, attn, rate)
-        ctx.csr, ctx.flags, ctx.scale = csr, flags, scale
+        ctx.csr, ctx.flags, ctx.scale, ctx.heads = csr, flags, scale, heads
         ctx.mark_non_differentiable(attn)
         return buf, attn
 
@@ -1620,22 +1671,23 @@ class FilmWAttnCatFunction(torch.autograd.Function):
 
 
 def film_wattn_cat(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
-                   scale: Optional[float] = None, return_weights: bool = False):
-    """``torch.cat((x, film_wattn(x, gb, w, csr, logits, scale)), dim=1)`` without a concatenation pass for the
-    aggregate."""
+                   scale: Optional[float] = None, return_weights: bool = False, heads: int = 1):
+    """``torch.cat((x, film_wattn(x, gb, w, csr, logits, scale, heads=heads)), dim=1)`` without a concatenation
+    pass for the aggregate."""
     _check_attn_degree(csr)
+    heads = _check_heads(heads, x.shape[1] if x.dim() == 4 else 0)  # host-side too
     _check_x(x)
-    buf, attn = FilmWAttnCatFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale)
+    buf, attn = FilmWAttnCatFunction.apply(x, gb, w, csr, _lib.GB_LOGITS if logits else 0, scale, heads)
     return (buf, attn) if return_weights else buf
 
 
 def film_wattn_residual(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, logits: bool = False,
-                        scale: Optional[float] = None) -> torch.Tensor:
+                        scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
     """``x + film_wattn(x, ...)`` (the sum by torch: no fused epilogue for this reducer)."""
-    return x + film_wattn(x, gb, w, csr, logits, scale)
+    return x + film_wattn(x, gb, w, csr, logits, scale, heads=heads)
 
 
 def film_wattn_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: GraphCSR, x0: torch.Tensor, alpha: float,
-                   logits: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+                   logits: bool = False, scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
     """``(1 - alpha) * film_wattn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
-    return (1.0 - float(alpha)) * film_wattn(x, gb, w, csr, logits, scale) + float(alpha) * x0
+    return (1.0 - float(alpha)) * film_wattn(x, gb, w, csr, logits, scale, heads=heads) + float(alpha) * x0

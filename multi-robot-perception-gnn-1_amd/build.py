@@ -17,6 +17,10 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "film_attn_fwd.hip",
                                                     "film_wattn_bwd.hip", "film_wattn_bwd_bf16.hip",
                                                     "film_wattn_bwd_f16.hip", "film_wattn_fwd.hip",
+                                                    "film_attn_mh_bwd.hip", "film_attn_mh_bwd_bf16.hip",
+                                                    "film_attn_mh_bwd_f16.hip", "film_attn_mh_fwd.hip",
+                                                    "film_wattn_mh_bwd.hip", "film_wattn_mh_bwd_bf16.hip",
+                                                    "film_wattn_mh_bwd_f16.hip", "film_wattn_mh_fwd.hip",
                                                     "film_wmean_bwd.hip", "film_wmean_bwd_bf16.hip",
                                                     "film_wmean_bwd_f16.hip", "film_wmean_fwd.hip",
                                                     "film_mean_fwd.hip",

@@ -827,7 +827,7 @@ class FilmCompressFunction(torch.autograd.Function):
     saved aggregate.  Saves x, gb and the aggregate — not a 2C-channel buffer."""
 
     @staticmethod
-    def forward(ctx, x, gb, weight, bias, csr, mode: int, reducer: str = "mean", scale=None):
+    def forward(ctx, x, gb, weight, bias, csr, mode: int, reducer: str = "mean", scale=None, heads: int = 1):
         from .aggregate import film_attn_forward_into, film_max_forward_into, film_mean_forward_into
         n, C, H, W = x.shape
         hip = _PATH[0] != "library"
@@ -843,14 +843,16 @@ class FilmCompressFunction(torch.autograd.Function):
         if reducer == "max":
             film_max_forward_into(x, gb, csr, mode, agg)
         elif reducer == "attn":
-            attn = film_attn_forward_into(x, gb, csr, mode, agg, scale)  # the weights: saved for the backward
+            # the weights: saved for the backward
+            attn = film_attn_forward_into(x, gb, csr, mode, agg, scale, heads=heads)
         else:
             film_mean_forward_into(x, gb, csr, mode, agg)
         prec = _PRECISION[0]  # read once: both gradients of this node run in the forward's mode
         y = _fwd(weight, bias, x, agg, cl=cl, precision=prec) if hip else _lib_forward(weight, bias, x, agg)
         ctx.save_for_backward(x, gb, agg, weight, bias, attn)
         ctx.csr, ctx.mode, ctx.has_bias, ctx.hip, ctx.cl, ctx.precision = csr, mode, bias is not None, hip, cl, prec
-        ctx.reducer, ctx.scale = reducer, scale  # the aggregation step and its backward dispatch on the reducer
+        # the aggregation step and its backward dispatch on the reducer
+        ctx.reducer, ctx.scale, ctx.heads = reducer, scale, heads
         return y
 
     @staticmethod
@@ -868,7 +870,7 @@ class FilmCompressFunction(torch.autograd.Function):
                                             grad_x_base=gx if need_x else None)
             elif ctx.reducer == "attn":
                 dx, dgb = film_attn_backward(ga, x, gb, attn, ctx.csr, ctx.mode, need_x, need_gb,
-                                             grad_x_base=gx if need_x else None, scale=ctx.scale)
+                                             grad_x_base=gx if need_x else None, scale=ctx.scale, heads=ctx.heads)
             else:
                 dx, dgb = film_mean_backward(ga, x, gb, ctx.csr, ctx.mode, need_x, need_gb,
                                              grad_x_base=gx if need_x else None,
@@ -881,7 +883,7 @@ class FilmCompressFunction(torch.autograd.Function):
                 _lib_backward_weight(gy, x, agg, ctx.has_bias)
             if not ctx.needs_input_grad[2]:
                 dw = None
-        return dx, dgb, dw, db, None, None, None, None
+        return dx, dgb, dw, db, None, None, None, None, None
 
 
 class FilmWMeanCompressFunction(torch.autograd.Function):
@@ -938,15 +940,21 @@ def film_compress_supported(conv: torch.nn.Conv2d, x: torch.Tensor) -> bool:
 
 
 def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int, reducer: str = "mean",
-                  scale=None, weights=None) -> torch.Tensor:
+                  scale=None, weights=None, heads: int = 1) -> torch.Tensor:
     """Autograd form of ``conv(torch.cat((x, film_mean(x, gb)), 1))`` without the concatenation
     (:class:`FilmCompressFunction`); the caller checks :func:`film_compress_supported`.  ``reducer="max"``:
     the aggregate is ``film_max(x, gb)`` and ``mode`` carries its flags (0 or ``GB_LOGITS``);
-    ``reducer="attn"``: likewise ``film_attn(x, gb, scale=scale)``; ``reducer="wmean"``: the aggregate is
+    ``reducer="attn"``: likewise ``film_attn(x, gb, scale=scale, heads=heads)``; ``reducer="wmean"``: the aggregate is
     ``film_wmean(x, gb, weights)`` with ``mode`` = ``MODE_FILM_MEAN`` or ``MODE_FILM_SUM`` (the normalised or
     the plain weighted sum), optionally with ``GB_LOGITS`` (:class:`FilmWMeanCompressFunction`)."""
     if reducer not in ("mean", "max", "attn", "wmean"):
         raise ValueError(f'reducer must be "mean", "max", "attn" or "wmean", got {reducer!r}')
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"heads must be a positive int, got {heads!r}")
+    if heads != 1 and reducer != "attn":
+        raise ValueError('heads belong to reducer="attn"')
+    if x.dim() == 4 and x.shape[1] % heads:
+        raise ValueError(f"heads must divide the channels: C = {x.shape[1]}, heads = {heads}")
     if (weights is not None) != (reducer == "wmean"):
         raise ValueError('weights belong to reducer="wmean", which needs them')
     if reducer == "wmean":
@@ -973,4 +981,4 @@ def film_compress(conv: torch.nn.Conv2d, x: torch.Tensor, gb, csr, mode: int, re
         raise ValueError('scale belongs to reducer="attn"')
     if gb is not None:
         gb = gb.reshape(csr.num_edges, x.shape[1], 2)
-    return FilmCompressFunction.apply(x, gb, conv.weight, conv.bias, csr, mode, reducer, scale)
+    return FilmCompressFunction.apply(x, gb, conv.weight, conv.bias, csr, mode, reducer, scale, heads)

@@ -1,5 +1,6 @@
 // film_attn_bwd.hip — backward launcher and C ABI of the attention-pooled FiLM aggregation
-// (mrp_film_attn_bwd), and the fp32 launches.  Kernels and design notes: film_attn_kernels.hpp; 16-bit launches:
+// (mrp_film_attn_bwd) and of its multi-head form (mrp_film_attn_bwd_mh; the MH launches: film_attn_mh_bwd*.hip),
+// and the fp32 launches.  Kernels and design notes: film_attn_kernels.hpp; 16-bit launches:
 // film_attn_bwd_{bf16,f16}.hip.
 #include "film_attn_kernels.hpp"
 
@@ -51,15 +52,18 @@ hipError_t launch_attn_dgb_reduce(const AttnArgs& m, int64_t blocks, hipStream_t
 }
 }  // namespace mrp_host
 
-extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x,
-                                 int64_t x_node_stride, const float* gb, const int32_t* indptr, const int32_t* src,
-                                 const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
-                                 int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
-                                 int32_t flags, void* grad_x, int64_t gx_node_stride, const void* grad_x_base,
-                                 int64_t base_node_stride, float* grad_gb, float scale, const float* attn,
-                                 void* workspace, int64_t workspace_bytes, void* stream) {
+namespace {
+
+// Both entry points; heads = 1 launches the single-head kernels.
+int attn_bwd(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x, int64_t x_node_stride,
+             const float* gb, const int32_t* indptr, const int32_t* src, const int32_t* eid, const int32_t* graph_off,
+             int32_t num_graphs, int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C,
+             int32_t P, int32_t flags, int32_t heads, void* grad_x, int64_t gx_node_stride, const void* grad_x_base,
+             int64_t base_node_stride, float* grad_gb, float scale, const float* attn, void* workspace,
+             int64_t workspace_bytes, void* stream) {
   if (!attn_common_ok(dtype, flags, indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind, num_nodes,
-                      num_edges, C, P, scale))
+                      num_edges, C, P, scale) ||
+      !attn_heads_ok(C, heads))
     return hipErrorInvalidValue;
   if (workspace_bytes < 0) return hipErrorInvalidValue;
   const bool want_dx = grad_x != nullptr, want_dgb = grad_gb != nullptr;
@@ -83,7 +87,8 @@ extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_
   const int ck = attn_bwd_chunk(max_nodes);
   const size_t lds = lds_attn(max_nodes, ck, true);
   const int64_t rblocks = ((int64_t)num_nodes * mrp::kAttnSlots * C + mrp::kBlock - 1) / mrp::kBlock;
-  if (!empty && (grid > 0x7fffffff || rblocks > 0x7fffffff || lds > kMaxDynamicLds)) return hipErrorInvalidValue;
+  if (!empty && (grid > 0x7fffffff || heads > kMaxGridY || rblocks > 0x7fffffff || lds > kMaxDynamicLds))
+    return hipErrorInvalidValue;
   // rows of grad_gb no CSR entry names are zeros (COMPLETE graphs name every row)
   if (want_dgb && !complete && num_edges > 0 && C > 0) {
     const hipError_t e = hipMemsetAsync(grad_gb, 0, (size_t)num_edges * C * 2 * sizeof(float), st);
@@ -124,10 +129,22 @@ extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_
   m.E = num_edges;
   const int ks = attn_slots_for(graph_kind, max_nodes);
   hipError_t rc;
-  switch (dtype) {
-    case MRP_DTYPE_F32: rc = launch_attn_bwd_f32(m, ck, ks, lds, grid, st); break;
-    case MRP_DTYPE_BF16: rc = launch_attn_bwd_bf16(m, ck, ks, lds, grid, st); break;
-    default: rc = launch_attn_bwd_f16(m, ck, ks, lds, grid, st); break;
+  if (heads > 1) {
+    mrp::AttnMhArgs<false> mh = {};
+    static_cast<AttnArgs&>(mh) = m;
+    mh.a.C = C / heads;
+    mh.gbC = C;
+    switch (dtype) {
+      case MRP_DTYPE_F32: rc = launch_attn_mh_bwd_f32(mh, ck, ks, lds, grid, heads, st); break;
+      case MRP_DTYPE_BF16: rc = launch_attn_mh_bwd_bf16(mh, ck, ks, lds, grid, heads, st); break;
+      default: rc = launch_attn_mh_bwd_f16(mh, ck, ks, lds, grid, heads, st); break;
+    }
+  } else {
+    switch (dtype) {
+      case MRP_DTYPE_F32: rc = launch_attn_bwd_f32(m, ck, ks, lds, grid, st); break;
+      case MRP_DTYPE_BF16: rc = launch_attn_bwd_bf16(m, ck, ks, lds, grid, st); break;
+      default: rc = launch_attn_bwd_f16(m, ck, ks, lds, grid, st); break;
+    }
   }
   if (rc != hipSuccess) return rc;
   if (a.want_dgb && ntile > 1) {
@@ -135,4 +152,31 @@ extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_
     rc = hipGetLastError();
   }
   return rc;
+}
+
+}  // namespace
+
+extern "C" int mrp_film_attn_bwd(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x,
+                                 int64_t x_node_stride, const float* gb, const int32_t* indptr, const int32_t* src,
+                                 const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                                 int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
+                                 int32_t flags, void* grad_x, int64_t gx_node_stride, const void* grad_x_base,
+                                 int64_t base_node_stride, float* grad_gb, float scale, const float* attn,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  return attn_bwd(dtype, grad_out, g_node_stride, x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs,
+                  max_nodes, graph_kind, num_nodes, num_edges, C, P, flags, 1, grad_x, gx_node_stride, grad_x_base,
+                  base_node_stride, grad_gb, scale, attn, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mrp_film_attn_bwd_mh(int32_t dtype, const void* grad_out, int64_t g_node_stride, const void* x,
+                                    int64_t x_node_stride, const float* gb, const int32_t* indptr, const int32_t* src,
+                                    const int32_t* eid, const int32_t* graph_off, int32_t num_graphs,
+                                    int32_t max_nodes, int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                                    int32_t C, int32_t P, int32_t flags, int32_t heads, void* grad_x,
+                                    int64_t gx_node_stride, const void* grad_x_base, int64_t base_node_stride,
+                                    float* grad_gb, float scale, const float* attn, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  return attn_bwd(dtype, grad_out, g_node_stride, x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs,
+                  max_nodes, graph_kind, num_nodes, num_edges, C, P, flags, heads, grad_x, gx_node_stride, grad_x_base,
+                  base_node_stride, grad_gb, scale, attn, workspace, workspace_bytes, stream);
 }

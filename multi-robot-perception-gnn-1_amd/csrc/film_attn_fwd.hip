@@ -1,5 +1,7 @@
 // film_attn_fwd.hip — forward launcher, workspace query and C ABI of the attention-pooled FiLM aggregation
-// (mrp_film_attn_fwd, mrp_film_attn_workspace).  Kernels and design notes: film_attn_kernels.hpp.
+// (mrp_film_attn_fwd, mrp_film_attn_workspace) and of its multi-head form (mrp_film_attn_fwd_mh,
+// mrp_film_attn_workspace_mh; the MH launches: film_attn_mh_fwd.hip).  Kernels and design notes:
+// film_attn_kernels.hpp.
 #include "film_attn_kernels.hpp"
 
 using namespace mrp_host;
@@ -18,6 +20,13 @@ hipError_t launch_attn_fwd(const AttnArgs& m, int ks, size_t lds, int64_t grid, 
   return hipGetLastError();
 }
 
+// Both entry points; heads = 1 launches the single-head kernels.
+int attn_fwd(int32_t dtype, const void* x, int64_t x_node_stride, const float* gb, const int32_t* indptr,
+             const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+             int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t flags,
+             int32_t heads, void* out, int64_t out_node_stride, float scale, float* attn, int64_t workspace_bytes,
+             void* stream);
+
 }  // namespace
 
 extern "C" int64_t mrp_film_attn_workspace(int32_t direction, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
@@ -30,6 +39,13 @@ extern "C" int64_t mrp_film_attn_workspace(int32_t direction, int32_t num_graphs
   return attn_workspace_bytes(num_edges, C, P);
 }
 
+extern "C" int64_t mrp_film_attn_workspace_mh(int32_t direction, int32_t num_graphs, int32_t max_nodes,
+                                              int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C,
+                                              int32_t P, int32_t heads) {
+  (void)heads;  // the grad_gb partials [tile][E][C][2] hold every head's columns
+  return mrp_film_attn_workspace(direction, num_graphs, max_nodes, graph_kind, num_nodes, num_edges, C, P);
+}
+
 extern "C" int mrp_film_attn_fwd(int32_t dtype, const void* x, int64_t x_node_stride, const float* gb,
                                  const int32_t* indptr, const int32_t* src, const int32_t* eid,
                                  const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind,
@@ -37,14 +53,39 @@ extern "C" int mrp_film_attn_fwd(int32_t dtype, const void* x, int64_t x_node_st
                                  int64_t out_node_stride, float scale, float* attn, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
   (void)workspace;
+  return attn_fwd(dtype, x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind,
+                  num_nodes, num_edges, C, P, flags, 1, out, out_node_stride, scale, attn, workspace_bytes, stream);
+}
+
+extern "C" int mrp_film_attn_fwd_mh(int32_t dtype, const void* x, int64_t x_node_stride, const float* gb,
+                                    const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                                    const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                                    int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P,
+                                    int32_t flags, int32_t heads, void* out, int64_t out_node_stride, float scale,
+                                    float* attn, void* workspace, int64_t workspace_bytes, void* stream) {
+  (void)workspace;
+  return attn_fwd(dtype, x, x_node_stride, gb, indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind,
+                  num_nodes, num_edges, C, P, flags, heads, out, out_node_stride, scale, attn, workspace_bytes,
+                  stream);
+}
+
+namespace {
+
+int attn_fwd(int32_t dtype, const void* x, int64_t x_node_stride, const float* gb, const int32_t* indptr,
+             const int32_t* src, const int32_t* eid, const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+             int32_t graph_kind, int32_t num_nodes, int32_t num_edges, int32_t C, int32_t P, int32_t flags,
+             int32_t heads, void* out, int64_t out_node_stride, float scale, float* attn, int64_t workspace_bytes,
+             void* stream) {
   if (!attn_common_ok(dtype, flags, indptr, src, eid, graph_off, num_graphs, max_nodes, graph_kind, num_nodes,
-                      num_edges, C, P, scale))
+                      num_edges, C, P, scale) ||
+      !attn_heads_ok(C, heads))
     return hipErrorInvalidValue;
   if (workspace_bytes < 0) return hipErrorInvalidValue;  // the forward's query is 0
   if (num_graphs == 0 || num_nodes == 0 || max_nodes == 0 || C == 0 || P == 0) {
     // nothing to score: no kernel runs, and the weights, if the caller passed a buffer, are zeros
     if (attn != nullptr && num_edges > 0 && P > 0)
-      return hipMemsetAsync(attn, 0, (size_t)num_edges * P * sizeof(float), static_cast<hipStream_t>(stream));
+      return hipMemsetAsync(attn, 0, (size_t)heads * num_edges * P * sizeof(float),
+                            static_cast<hipStream_t>(stream));
     return hipSuccess;
   }
   const int64_t plane = (int64_t)C * P;
@@ -53,11 +94,11 @@ extern "C" int mrp_film_attn_fwd(int32_t dtype, const void* x, int64_t x_node_st
   const int ntile = attn_tiles(P);
   const int64_t grid = (int64_t)num_graphs * ntile;
   const size_t lds = lds_attn(max_nodes, mrp::kAttnFwdChunk, false);
-  if (grid > 0x7fffffff || lds > kMaxDynamicLds) return hipErrorInvalidValue;
+  if (grid > 0x7fffffff || heads > kMaxGridY || lds > kMaxDynamicLds) return hipErrorInvalidValue;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // rows of attn no CSR entry names are zeros (COMPLETE graphs name every row)
+  // rows of attn no CSR entry names are zeros (COMPLETE graphs name every row), in every head
   if (graph_kind != MRP_GRAPH_COMPLETE && num_edges > 0) {
-    const hipError_t e = hipMemsetAsync(attn, 0, (size_t)num_edges * P * sizeof(float), st);
+    const hipError_t e = hipMemsetAsync(attn, 0, (size_t)heads * num_edges * P * sizeof(float), st);
     if (e != hipSuccess) return e;
   }
   AttnArgs m = {};
@@ -84,9 +125,18 @@ extern "C" int mrp_film_attn_fwd(int32_t dtype, const void* x, int64_t x_node_st
   m.attn = attn;
   m.E = num_edges;
   const int ks = attn_slots_for(graph_kind, max_nodes);
+  if (heads > 1) {
+    mrp::AttnMhArgs<false> mh = {};
+    static_cast<AttnArgs&>(mh) = m;
+    mh.a.C = C / heads;
+    mh.gbC = C;
+    return launch_attn_mh_fwd(dtype, mh, ks, lds, grid, heads, st);
+  }
   switch (dtype) {
     case MRP_DTYPE_F32: return launch_attn_fwd<float>(m, ks, lds, grid, st);
     case MRP_DTYPE_BF16: return launch_attn_fwd<mrp::bf16_t>(m, ks, lds, grid, st);
     default: return launch_attn_fwd<mrp::f16_t>(m, ks, lds, grid, st);
   }
 }
+
+}  // namespace

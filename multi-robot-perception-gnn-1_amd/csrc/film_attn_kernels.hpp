@@ -43,6 +43,15 @@
 // ascending order: the waves take turns, one destination at a time, on one lane-private LDS cell per (node,
 // pixel) — at most 16 barriers per workgroup, one writer per element, no atomics.  WGT = false compiles the
 // statements film_attn always had.
+//
+// MH = true instantiates the same kernels as the multi-head operators (mrp_film_attn_*_mh, mrp_film_wattn_*_mh,
+// film_attn_mh_*.hip): the grid gains a head factor (blockIdx.y), and a workgroup rebases its argument block to
+// its head — x, out, grad_out, grad_x and its base by head * Ch * P elements, gb / grad_gb / the grad_gb workspace
+// by head * Ch channel columns, attn / rate by head * E * P, a.C = Ch — and then runs the single-head statements.
+// Only the row stride of gb (the full C, gbC below) differs from a.C, so chunk boundaries count from the head's
+// first channel and head k's bits are those of a single-head launch on the channel slice.  grad_w crosses heads:
+// each head writes its in-workgroup sum to a partial (H, nodes, P) and film_attn_gw_reduce adds them, heads
+// ascending.  MH = false compiles the statements the single-head kernels always had.
 
 #include <type_traits>
 
@@ -79,6 +88,45 @@ struct WAttnArgs : AttnArgs {
 };
 template <bool WGT>
 using AttnArgsOf = std::conditional_t<WGT, WAttnArgs, AttnArgs>;
+
+// The MH kernels' argument block: a.C holds the channels of one head, gbC the channels of gb's rows.
+template <bool WGT>
+struct AttnMhArgs : AttnArgsOf<WGT> {
+  int32_t gbC;   // C: the channel stride of gb, grad_gb and the grad_gb workspace
+  int64_t gwhs;  // WGT backward: elements between two heads' grad_w partials (gw points at head 0's)
+};
+template <bool WGT, bool MH>
+using AttnKernelArgs = std::conditional_t<MH, AttnMhArgs<WGT>, AttnArgsOf<WGT>>;
+
+// MH: rebase the argument block to this workgroup's head (blockIdx.y): what a single-head launch on the head's
+// channel slice would get.
+template <typename T, bool WGT>
+__device__ __forceinline__ void attn_head_rebase(AttnMhArgs<WGT>& m) {
+  AggArgs& a = m.a;
+  const int64_t k = blockIdx.y;
+  const int64_t xoff = k * a.C * a.P, goff = k * a.C * 2, eoff = k * m.E * a.P;
+  a.x = static_cast<const T*>(a.x) + xoff;
+  if (a.g != nullptr) a.g = static_cast<const T*>(a.g) + xoff;
+  if (a.out != nullptr) a.out = static_cast<T*>(a.out) + xoff;
+  if (a.dxb != nullptr) a.dxb = static_cast<const T*>(a.dxb) + xoff;
+  if (a.gb != nullptr) a.gb += goff;
+  if (a.dgb != nullptr) a.dgb += goff;
+  if (m.ws != nullptr) m.ws += goff;
+  if (m.attn != nullptr) m.attn += eoff;
+  if constexpr (WGT) {
+    if (m.rate != nullptr) m.rate += eoff;
+    if (m.gw != nullptr) m.gw += k * m.gwhs;
+  }
+}
+
+// the channels of gb's rows
+template <bool MH, typename Args>
+__device__ __forceinline__ int attn_gb_channels(const Args& m) {
+  if constexpr (MH)
+    return m.gbC;
+  else
+    return m.a.C;
+}
 
 // LDS of one workgroup for graphs of up to nmax nodes and chunks of ck channels.
 struct AttnLds {
@@ -162,10 +210,10 @@ struct AttnChunk {
 
 // Issue the loads of chunk [c0, c0 + CK) (zeros past C, past the graph's nodes and past the plane's end).
 // my_e: the edge id of slot threadIdx.x (-1: none).  with_base (wave-uniform): also grad_x_base, which only the
-// backward's second sweep reads.
-template <int CK, bool BWD, typename T>
+// backward's second sweep reads.  MH: gbC is the channels of gb's rows (else a.C, read here as it always was).
+template <int CK, bool BWD, typename T, bool MH = false>
 __device__ __forceinline__ void attn_fetch(const AttnArgs& m, int node0, int n, int c0, int p, bool pin, int my_e,
-                                           AttnChunk<CK, BWD, T>& r, bool with_base = false) {
+                                           AttnChunk<CK, BWD, T>& r, bool with_base = false, int gbC = 0) {
   const AggArgs& a = m.a;
   const int wave = threadIdx.x >> 6;
   const int ck = min(CK, a.C - c0);  // <= 0 past the last chunk: nothing is loaded
@@ -194,7 +242,11 @@ __device__ __forceinline__ void attn_fetch(const AttnArgs& m, int node0, int n, 
       }
     }
     float2 w = make_float2(0.f, 0.f);
+    if constexpr (MH) {
+      if (cl < ck && my_e >= 0) w = *reinterpret_cast<const float2*>(a.gb + ((int64_t)my_e * gbC + c0 + cl) * 2);
+    } else {
     if (cl < ck && my_e >= 0) w = *reinterpret_cast<const float2*>(a.gb + ((int64_t)my_e * a.C + c0 + cl) * 2);
+    }
     r.w[cl] = w;
   }
 }
@@ -302,8 +354,9 @@ __device__ __forceinline__ float wave_sum63(float x) {
 // Forward.  Workgroup = graph x pixel tile.  KS: compiled slots per destination (4, 8 or 16; the launcher picks
 // KS >= the graph kind's in-degree bound).
 // ---------------------------------------------------------------------------
-template <typename T, int KS, bool WGT = false>
-__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
+template <typename T, int KS, bool WGT = false, bool MH = false>
+__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnKernelArgs<WGT, MH> m) {
+  if constexpr (MH) attn_head_rebase<T, WGT>(m);
   const AggArgs& a = m.a;
   extern __shared__ float4 smem_f4[];
   const AttnLds L(smem_f4, a.nmax, kAttnFwdChunk, false);
@@ -320,7 +373,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
   constexpr int CK = kAttnFwdChunk;
   const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
   AttnChunk<CK, false, T> next;
-  attn_fetch<CK, false, T>(m, node0, n, 0, p, pin, my_e, next);
+  attn_fetch<CK, false, T, MH>(m, node0, n, 0, p, pin, my_e, next, false, attn_gb_channels<MH>(m));
 
   float s[kAttnDpw][KS];
 #pragma unroll
@@ -331,7 +384,8 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
   // sweep A: the scores, each an ascending chain over the channels
   for (int c0 = 0; c0 < a.C; c0 += CK) {
     attn_put<CK, false, T>(m, L, n, my_e, next);
-    attn_fetch<CK, false, T>(m, node0, n, c0 + CK < a.C ? c0 + CK : 0, p, pin, my_e, next);  // wraps: sweep B's first
+    attn_fetch<CK, false, T, MH>(m, node0, n, c0 + CK < a.C ? c0 + CK : 0, p, pin, my_e, next, false,
+                                attn_gb_channels<MH>(m));  // wraps: sweep B's first
     attn_scores<false, KS>(m, L, n, min(CK, a.C - c0), s);
   }
 
@@ -410,7 +464,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
   for (int c0 = 0; c0 < a.C; c0 += CK) {
     const int ck = min(CK, a.C - c0);
     attn_put<CK, false, T>(m, L, n, my_e, next);
-    attn_fetch<CK, false, T>(m, node0, n, c0 + CK, p, pin, my_e, next);
+    attn_fetch<CK, false, T, MH>(m, node0, n, c0 + CK, p, pin, my_e, next, false, attn_gb_channels<MH>(m));
 #pragma unroll
     for (int i = 0; i < kAttnDpw; ++i) {
       const int v = wave + kAttnWaves * i;
@@ -454,8 +508,9 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnArgsOf<WGT> m) {
 // Backward.  Workgroup = graph x pixel tile; a.want_dx / a.want_dgb choose the outputs (the arithmetic of
 // either is the same whether or not the other is wanted).  CK: channels per chunk; KS as in the forward.
 // ---------------------------------------------------------------------------
-template <typename T, int CK, int KS, bool WGT = false>
-__global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
+template <typename T, int CK, int KS, bool WGT = false, bool MH = false>
+__global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnKernelArgs<WGT, MH> m) {
+  if constexpr (MH) attn_head_rebase<T, WGT>(m);
   const AggArgs& a = m.a;
   extern __shared__ float4 smem_f4[];
   const AttnLds L(smem_f4, a.nmax, CK, true);
@@ -471,7 +526,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
   attn_tables(m, L, b, node0, n);
   const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
   AttnChunk<CK, true, T> next;
-  attn_fetch<CK, true, T>(m, node0, n, 0, p, pin, my_e, next);
+  attn_fetch<CK, true, T, MH>(m, node0, n, 0, p, pin, my_e, next, false, attn_gb_channels<MH>(m));
 
   float ds[kAttnDpw][KS], at[kAttnDpw][KS];
 #pragma unroll
@@ -483,7 +538,8 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
   for (int c0 = 0; c0 < a.C; c0 += CK) {
     attn_put<CK, true, T>(m, L, n, my_e, next);
     const bool last = c0 + CK >= a.C;  // then the fetch wraps to sweep B's first chunk, base included
-    attn_fetch<CK, true, T>(m, node0, n, last ? 0 : c0 + CK, p, pin, my_e, next, last);
+    attn_fetch<CK, true, T, MH>(m, node0, n, last ? 0 : c0 + CK, p, pin, my_e, next, last,
+                                   attn_gb_channels<MH>(m));
     attn_scores<true, KS>(m, L, n, min(CK, a.C - c0), ds);
   }
   unsigned dmask[kAttnDpw];  // WGT: bit j: entry j of destination i delivered at this lane's pixel
@@ -571,7 +627,7 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
     T base[CK * kAttnDpw];  // this chunk's grad_x_base, kept while the next chunk is fetched
 #pragma unroll
     for (int t = 0; t < CK * kAttnDpw; ++t) base[t] = next.b[t];
-    attn_fetch<CK, true, T>(m, node0, n, c0 + CK, p, pin, my_e, next, true);
+    attn_fetch<CK, true, T, MH>(m, node0, n, c0 + CK, p, pin, my_e, next, true, attn_gb_channels<MH>(m));
     float* Dw = L.D + wave * CK * a.nmax * kAttnTile + lane;  // this lane's partials: [cl][u]
     if (want_dx) {
       // lane-private: written after the barriers that ended the previous chunk's sum, read by this lane only
@@ -614,9 +670,9 @@ __global__ void __launch_bounds__(kBlock) film_attn_bwd(AttnArgsOf<WGT> m) {
             float2 rsum = make_float2(wave_sum63(used ? __fmul_rn(xu[jj], dm) : 0.f), wave_sum63(dm));
             if (lane == 63 && jj < r.deg) {
               const int e = L.slot_e[v * kAttnSlots + jj];
-              const int64_t off = ((int64_t)e * a.C + c) * 2;
+              const int64_t off = ((int64_t)e * attn_gb_channels<MH>(m) + c) * 2;
               if (m.ntile > 1) {
-                *reinterpret_cast<float2*>(m.ws + (int64_t)tile * m.E * a.C * 2 + off) = rsum;
+                *reinterpret_cast<float2*>(m.ws + (int64_t)tile * m.E * attn_gb_channels<MH>(m) * 2 + off) = rsum;
               } else {
                 if (a.logits) rsum = sigmoid_backward(rsum, *reinterpret_cast<const float2*>(a.gb + off));
                 *reinterpret_cast<float2*>(a.dgb + off) = rsum;
@@ -706,10 +762,43 @@ hipError_t launch_wattn_bwd_f16(const WAttnArgs& m, int ck, int ks, size_t lds, 
 // film_attn_dgb_reduce (film_attn_bwd.hip) over `blocks` workgroups
 hipError_t launch_attn_dgb_reduce(const AttnArgs& m, int64_t blocks, hipStream_t st);
 
-template <typename T, bool WGT = false>
-hipError_t launch_attn_bwd(const mrp::AttnArgsOf<WGT>& m, int ck, int ks, size_t lds, int64_t grid, hipStream_t st) {
-  const dim3 g((unsigned)grid), block(mrp::kBlock);
-#define MRP_ATTN_BWD(CK, KS) hipLaunchKernelGGL((mrp::film_attn_bwd<T, CK, KS, WGT>), g, block, lds, st, m)
+// the multi-head instantiations (film_attn_mh_bwd*.hip); grid = graphs x tiles, the head factor is heads
+hipError_t launch_attn_mh_bwd_f32(const mrp::AttnMhArgs<false>& m, int ck, int ks, size_t lds, int64_t grid, int heads,
+                                  hipStream_t st);
+hipError_t launch_attn_mh_bwd_bf16(const mrp::AttnMhArgs<false>& m, int ck, int ks, size_t lds, int64_t grid,
+                                   int heads, hipStream_t st);
+hipError_t launch_attn_mh_bwd_f16(const mrp::AttnMhArgs<false>& m, int ck, int ks, size_t lds, int64_t grid, int heads,
+                                  hipStream_t st);
+hipError_t launch_wattn_mh_bwd_f32(const mrp::AttnMhArgs<true>& m, int ck, int ks, size_t lds, int64_t grid, int heads,
+                                   hipStream_t st);
+hipError_t launch_wattn_mh_bwd_bf16(const mrp::AttnMhArgs<true>& m, int ck, int ks, size_t lds, int64_t grid,
+                                    int heads, hipStream_t st);
+hipError_t launch_wattn_mh_bwd_f16(const mrp::AttnMhArgs<true>& m, int ck, int ks, size_t lds, int64_t grid, int heads,
+                                   hipStream_t st);
+// the multi-head forwards (film_attn_mh_fwd.hip)
+hipError_t launch_attn_mh_fwd(int32_t dtype, const mrp::AttnMhArgs<false>& m, int ks, size_t lds, int64_t grid,
+                              int heads, hipStream_t st);
+hipError_t launch_wattn_mh_fwd(int32_t dtype, const mrp::AttnMhArgs<true>& m, int ks, size_t lds, int64_t grid,
+                               int heads, hipStream_t st);
+// film_attn_gw_reduce (film_attn_mh_fwd.hip): grad_w (nodes, P), node stride gwst, from the heads' partials
+hipError_t launch_attn_gw_reduce(const float* part, int heads, int32_t nodes, int32_t P, float* gw, int64_t gwst,
+                                 hipStream_t st);
+
+constexpr int kMaxGridY = 65535;  // the head factor of the grid
+
+// heads of a multi-head call: >= 1 and a divisor of C (C = 0: any)
+inline bool attn_heads_ok(int32_t C, int32_t heads) { return heads >= 1 && (C <= 0 || C % heads == 0); }
+
+// bytes of the multi-head backward's grad_w partials (H, nodes, P)
+inline int64_t attn_gw_partial_bytes(int32_t heads, int32_t num_nodes, int32_t P) {
+  return heads > 1 ? (int64_t)heads * num_nodes * P * (int64_t)sizeof(float) : 0;
+}
+
+template <typename T, bool WGT = false, bool MH = false>
+hipError_t launch_attn_bwd(const mrp::AttnKernelArgs<WGT, MH>& m, int ck, int ks, size_t lds, int64_t grid,
+                           hipStream_t st, int heads = 1) {
+  const dim3 g((unsigned)grid, (unsigned)heads), block(mrp::kBlock);
+#define MRP_ATTN_BWD(CK, KS) hipLaunchKernelGGL((mrp::film_attn_bwd<T, CK, KS, WGT, MH>), g, block, lds, st, m)
   if (ck == mrp::kAttnBwdChunkSmall) {  // <= 8 nodes: in-degree <= 8 for every kind but CSR / SIMPLE rows
     if (ks == 4)
       MRP_ATTN_BWD(mrp::kAttnBwdChunkSmall, 4);

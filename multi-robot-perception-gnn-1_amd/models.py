@@ -29,7 +29,11 @@ Semantics switch ``opt.gcn_return``:
 attention over the messages: :func:`aggregate.film_attn`, every in-degree <= 16; ``opt.gcn_attn_scale``
 sets the score scale, default ``None``: 1/sqrt(C)), ``'film_wattn'`` (the same attention over what each sender's
 confidence map delivered: :func:`aggregate.film_wattn`, with the maps of ``opt.gcn_confidence`` or ``weights=``;
-with neither it is ``'film_attn'`` itself, same kernels, same bits).
+with neither it is ``'film_attn'`` itself, same kernels, same bits).  ``opt.gcn_attn_heads = H`` (absent or 1:
+nothing changes) makes both attention modes multi-head: H independent channel groups of C/H channels, each with
+its own scores and softmax, in one launch (``heads=`` of :func:`aggregate.film_attn`; the default scale becomes
+1/sqrt(C/H)).  It adds no parameter; a value that is not a positive int dividing ``feature_dim``, or any value
+but 1 under another ``gcn_mode``, is a ``ValueError`` when the module is built.
 
 ``opt.gcn_message_dtype``: ``None`` (default: nothing changes), ``'fp8_e4m3'`` or ``'fp8_e5m2'`` — the
 feature maps every GCN layer aggregates are quantised per node to OCP FP8, as each robot would transmit them
@@ -165,6 +169,22 @@ def _check_weighted(opt) -> None:
         raise ValueError("confidence-weighted aggregation is not provided together with gcn_message_dtype")
 
 
+def attn_heads(opt) -> int:
+    """``opt.gcn_attn_heads`` (absent: 1), checked: a positive int that divides ``opt.feature_dim``, and 1 unless
+    ``opt.gcn_mode`` is ``'film_attn'`` or ``'film_wattn'`` (``ValueError``, raised when a module is built)."""
+    heads = _opt(opt, "gcn_attn_heads", 1)
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"gcn_attn_heads must be a positive int, got {heads!r}")
+    if heads == 1:
+        return 1
+    mode = _opt(opt, "gcn_mode", "film_mean")
+    if mode not in ("film_attn", "film_wattn"):
+        raise ValueError(f"gcn_attn_heads={heads} is not provided for gcn_mode={mode!r} (film_attn, film_wattn)")
+    if opt.feature_dim % heads:
+        raise ValueError(f"gcn_attn_heads must divide feature_dim: {opt.feature_dim} % {heads} != 0")
+    return heads
+
+
 #: ``gcn_return`` given to a GCN unpickled from a reference checkpoint whose ``opt`` has none (see
 #: :meth:`GCN.__setstate__`); ``compat.reference_class_path(gcn_return=...)`` sets it.
 UNPICKLED_GCN_RETURN = "input"
@@ -180,6 +200,7 @@ class GCN(_PackedImages, nn.Module):
         if fmt is not None and _opt(opt, "gcn_mode", "film_mean") == "film_wattn":
             raise ValueError("gcn_message_dtype is not provided for gcn_mode='film_wattn' "
                              "(film_mean, film_sum, copy_mean)")
+        attn_heads(opt)  # a gcn_attn_heads the attention modes cannot take: ValueError here
         self.edge_encoder = edge_encoder(layers_dim=[opt.feature_dim, opt.feature_dim])
         if confidence_options(opt)[0]:  # a forbidden combination: ValueError here
             self.confidence = nn.Conv2d(opt.feature_dim, 1, kernel_size=1)
@@ -208,6 +229,10 @@ class GCN(_PackedImages, nn.Module):
     def _attn_scale(self):
         """``opt.gcn_attn_scale``: the score scale of ``gcn_mode='film_attn'`` (None: 1/sqrt(C))."""
         return _opt(self.opt, "gcn_attn_scale", None)
+
+    def _attn_heads(self) -> int:
+        """``opt.gcn_attn_heads``: the heads of ``gcn_mode='film_attn'`` / ``'film_wattn'`` (absent: 1)."""
+        return attn_heads(self.opt)
 
     def confidence_map(self, x: torch.Tensor) -> torch.Tensor:
         """The sender maps w (N, 1, H, W) fp32 of feature maps x: ``sigmoid(confidence(x))``, hard-gated by
@@ -284,7 +309,7 @@ class GCN(_PackedImages, nn.Module):
             return x  # models.py:226 returns the input; update_all's result is never read
         if w is not None:
             if self._wattn():
-                return film_wattn(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
+                return film_wattn(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean(x, gb, w, csr, wmode, logits=logits)
         mode = _opt(self.opt, "gcn_mode", "film_mean")
@@ -295,7 +320,7 @@ class GCN(_PackedImages, nn.Module):
         if mode == "film_max":  # the max reducer: an operator of its own (aggregate.film_max)
             return film_max(x, z, g.csr(x.device), logits=True)
         if mode in ("film_attn", "film_wattn"):  # per-location attention over the messages (aggregate.film_attn)
-            return film_attn(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
+            return film_attn(x, z, g.csr(x.device), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
         return film_mean(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_cat(self, g, feats: torch.Tensor = None, weights: torch.Tensor = None) -> torch.Tensor:
@@ -314,7 +339,7 @@ class GCN(_PackedImages, nn.Module):
             return cat
         if w is not None and self._return_mode() != "input":
             if self._wattn():
-                return film_wattn_cat(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
+                return film_wattn_cat(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_cat(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -326,7 +351,7 @@ class GCN(_PackedImages, nn.Module):
         if mode == "film_max":
             return film_max_cat(x, z, g.csr(x.device), logits=True)
         if mode in ("film_attn", "film_wattn"):
-            return film_attn_cat(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
+            return film_attn_cat(x, z, g.csr(x.device), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
 
@@ -376,7 +401,7 @@ class GCN(_PackedImages, nn.Module):
                 return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="max")
             if mode in ("film_attn", "film_wattn"):
                 return film_compress(conv, x, z, g.csr(x.device), _lib_logits(), reducer="attn",
-                                     scale=self._attn_scale())
+                                     scale=self._attn_scale(), heads=self._attn_heads())
             return film_compress(conv, x, z, g.csr(x.device), _lib_modes()[mode] | _lib_logits())
         return compress_1x1(conv, self.forward_cat(g, x))
 
@@ -390,7 +415,7 @@ class GCN(_PackedImages, nn.Module):
             return self._aggregate_q(g, x, fmt, per, x0=x, x0_scale=1.0)
         if w is not None and self._return_mode() != "input":
             if self._wattn():
-                return film_wattn_residual(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale())
+                return film_wattn_residual(*self._wattn_args(g, x, w), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_residual(x, gb, w, csr, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -402,7 +427,7 @@ class GCN(_PackedImages, nn.Module):
         if mode == "film_max":
             return film_max_residual(x, z, g.csr(x.device), logits=True)
         if mode in ("film_attn", "film_wattn"):
-            return film_attn_residual(x, z, g.csr(x.device), logits=True, scale=self._attn_scale())
+            return film_attn_residual(x, z, g.csr(x.device), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
         return film_mean_residual(x, z, g.csr(x.device), mode, logits=True)
 
     def forward_mix(self, g, feats: torch.Tensor, x0: torch.Tensor, alpha: float,
@@ -416,7 +441,7 @@ class GCN(_PackedImages, nn.Module):
             return self._aggregate_q(g, x, fmt, per, x0=x0, agg_scale=1.0 - float(alpha), x0_scale=float(alpha))
         if w is not None and self._return_mode() != "input":
             if self._wattn():
-                return film_wattn_mix(*self._wattn_args(g, x, w), x0, alpha, logits=True, scale=self._attn_scale())
+                return film_wattn_mix(*self._wattn_args(g, x, w), x0, alpha, logits=True, scale=self._attn_scale(), heads=self._attn_heads())
             gb, csr, wmode, logits = self._wmean_args(g, x)
             return film_wmean_mix(x, gb, w, csr, x0, alpha, wmode, logits=logits)
         if self._return_mode() == "input" or not x.is_cuda:
@@ -428,7 +453,7 @@ class GCN(_PackedImages, nn.Module):
         if mode == "film_max":
             return film_max_mix(x, z, g.csr(x.device), x0, alpha, logits=True)
         if mode in ("film_attn", "film_wattn"):
-            return film_attn_mix(x, z, g.csr(x.device), x0, alpha, logits=True, scale=self._attn_scale())
+            return film_attn_mix(x, z, g.csr(x.device), x0, alpha, logits=True, scale=self._attn_scale(), heads=self._attn_heads())
         return film_mean_mix(x, z, g.csr(x.device), x0, alpha, mode, logits=True)
 
 

@@ -57,7 +57,11 @@
  *    mrp_compress_fwd_split.  FP8 messages (mrp_film_mean_fwd_q): an E4M3 NaN code (0x7f / 0xff) and an
  *    E5M2 inf / NaN code decode to fp32 NaN / inf and from there propagate as above — to the destinations
  *    that consume that source, at that channel and pixel, and to no other element; FP8 subnormal codes are
- *    decoded exactly (no flush), and the product with the scale is one fp32 rounding.
+ *    decoded exactly (no flush), and the product with the scale is one fp32 rounding.  The same holds for
+ *    mrp_film_max_fwd_q, mrp_film_attn_fwd_q and mrp_film_wattn_fwd_q: a NaN / inf code is a NaN / inf message
+ *    element and reaches what it reaches in the fp32 operator on x^ (attention: every channel of that head
+ *    at that pixel of the consuming destinations, no other head; a sender silent at a pixel is never read
+ *    there); a non-finite query element acts as a non-finite x[v] does in mrp_film_attn_fwd, on v alone.
  */
 #ifndef MRP_GNN_H
 #define MRP_GNN_H
@@ -1451,7 +1455,8 @@ int mrp_film_mean_bwd_plan(int32_t dtype,
  * mode flags, self_scale != 0 or xcopy != NULL.  Zero sizes succeed without a launch.  No host
  * synchronisation; stream-capturable.  mrp_film_mean_fwd_q_plan: the same arguments without the stream,
  * host only (no GPU call), reporting the plan the launcher acts on (as mrp_film_mean_fwd_plan).
- * Not provided: pixel-major FP8 inputs, FP8 outputs, film_max / film_attn on FP8, a backward that reads FP8.
+ * Not provided: pixel-major FP8 inputs, FP8 outputs, a backward that reads FP8.  (The max and attention
+ * reducers on FP8: mrp_film_max_fwd_q / mrp_film_attn_fwd_q / mrp_film_wattn_fwd_q below.)
  */
 enum mrp_qdtype { MRP_QDTYPE_E4M3 = 0, MRP_QDTYPE_E5M2 = 1 };
 
@@ -1480,6 +1485,89 @@ int mrp_film_mean_fwd_q_plan(int32_t qdtype,
                              const mrp_agg_epilogue* epilogue,
                              mrp_agg_plan* plan);
 
+/*
+ * FP8 messages for the max and attention reducers, receiver side.  Added to ABI 22 without a new number
+ * (nothing existing changed).  A receiver holds its own features at full precision and is handed its
+ * neighbours' feature maps as FP8 codes with scales (and, for the gated fusion, their confidence maps):
+ *
+ *   xq, xq_node_stride, x_scale, qdtype   the messages, exactly as mrp_film_mean_fwd_q's xq / x_scale:
+ *            x^[u, c, p] = fl32(x_scale[u, c] * decode(xq[u, c, p])), x_scale (num_nodes, C) contiguous or
+ *            NULL (all 1), strides in elements = bytes.
+ *   query, query_node_stride, dtype       (attention only) the own features (num_nodes, C, P) of `dtype`
+ *            (MRP_DTYPE_F32, _BF16 or _F16), which is also the type of out.  A robot's own maps never
+ *            cross the link: x[v] scores the messages, x^[u] forms them, and the two are separate tensors.
+ *   out_dtype                             (max only: it has no query) the type of out.
+ *
+ *   mrp_film_max_fwd_q    out[v, c, p] = max_j fl(fl(gamma_j[c] x^[u_j, c, p]) + beta_j[c]); everything else
+ *                         as mrp_film_max_fwd.  == out_dtype(mrp_film_max_fwd(fp32 x^)) bit for bit.
+ *   mrp_film_attn_fwd_q   mrp_film_attn_fwd_mh with the messages formed from x^ and the scores from
+ *                         `query`: s_j[p] = scale * sum_c query[v, c, p] * m_j[c, p].  Everything else —
+ *                         gb, the graph, flags, heads, scale, attn (heads, E, P), the workspace arguments
+ *                         (the forward needs none) — as mrp_film_attn_fwd_mh; heads = 1 runs the
+ *                         single-head kernels.  With query = x^ in fp32 the result is mrp_film_attn_fwd_mh(x^)'s
+ *                         bit for bit, out and attn; a 16-bit query is widened exactly and out is rounded
+ *                         once at the store, so T(query) gives T(the fp32 call on float(query)) with the same
+ *                         attn.
+ *   mrp_film_wattn_fwd_q  the same for mrp_film_wattn_fwd_mh: w, w_node_stride and rate as there.
+ *   Under heads > 1, head k reads channels [k C / heads, (k + 1) C / heads) of xq, query and of x_scale's
+ *   rows: its bits are those of a single-head call on the slices.
+ *
+ * Special values: as mrp_film_mean_fwd_q — an E4M3 NaN code or an E5M2 inf / NaN code is a NaN / inf message
+ * element, and reaches what an fp32 NaN / inf at that place reaches in mrp_film_max_fwd / mrp_film_attn_fwd_mh
+ * / mrp_film_wattn_fwd_mh: in the attention forms the outputs (all channels of that head) of the destinations
+ * that consume that source at that pixel, no other head and no other pixel; a sender that is silent at a pixel
+ * (w <= 0) is never read there, whatever its codes.
+ * Return codes, all before any launch: hipErrorInvalidValue for an unknown qdtype, dtype or out_dtype; a NULL
+ * xq, query, out (or gb / attn with num_edges > 0, or w) with work to do; a node stride < C * P (w: < P);
+ * max_nodes > MRP_MAX_NODES or a REGULAR in-degree > 16 (CSR / SIMPLE rows longer than 16 are the
+ * caller's to reject, as for mrp_film_attn_fwd); heads < 1 or not dividing C; an unknown graph kind or flags
+ * other than 0 / MRP_AGG_GB_LOGITS; a non-finite scale; workspace_bytes < 0.  Zero sizes succeed without a
+ * launch (attn and rate, where passed, are zeroed as in mrp_film_attn_fwd_mh).  No host synchronisation;
+ * stream-capturable.  All offsets are 64-bit.
+ * Not provided: a backward (training through FP8 attention needs the query / source split in the backward
+ * kernels too), FP8 with mrp_film_wmean_fwd, pixel-major FP8, FP8 outputs, block scales.
+ */
+int mrp_film_max_fwd_q(int32_t qdtype,
+                       const void* xq, int64_t xq_node_stride,
+                       const float* x_scale,
+                       int32_t out_dtype,
+                       const float* gb,
+                       const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                       const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                       int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                       int32_t C, int32_t P, int32_t flags,
+                       void* out, int64_t out_node_stride,
+                       void* stream);
+int mrp_film_attn_fwd_q(int32_t qdtype,
+                        const void* xq, int64_t xq_node_stride,
+                        const float* x_scale,
+                        int32_t dtype,
+                        const void* query, int64_t query_node_stride,
+                        const float* gb,
+                        const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                        const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                        int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                        int32_t C, int32_t P, int32_t flags, int32_t heads,
+                        void* out, int64_t out_node_stride,
+                        float scale, float* attn,
+                        void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int mrp_film_wattn_fwd_q(int32_t qdtype,
+                         const void* xq, int64_t xq_node_stride,
+                         const float* x_scale,
+                         int32_t dtype,
+                         const void* query, int64_t query_node_stride,
+                         const float* gb,
+                         const float* w, int64_t w_node_stride,
+                         const int32_t* indptr, const int32_t* src, const int32_t* eid,
+                         const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes,
+                         int32_t graph_kind, int32_t num_nodes, int32_t num_edges,
+                         int32_t C, int32_t P, int32_t flags, int32_t heads,
+                         void* out, int64_t out_node_stride,
+                         float scale, float* attn, float* rate,
+                         void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* Library identification: ABI version (incremented on signature changes; 22 = this header: v21 plus
  * the typed aggregation entry points mrp_film_mean_fwd_t / mrp_film_mean_bwd_t (bf16 and fp16 feature
  * tensors, enum mrp_dtype) and, added since without a new number (nothing existing changed), the
@@ -1490,7 +1578,8 @@ int mrp_film_mean_fwd_q_plan(int32_t qdtype,
  * mrp_compress_fwd_split_p / _bwd_data_split_p / _bwd_weight_split_p, and their pixel-major fp32 forms
  * mrp_compress_fwd_split_cl / _bwd_data_split_cl / _bwd_weight_split_cl_workspace / _bwd_weight_split_cl
  * with the knobs "compress_split_cl" / "split_cl_splits", and the host-only plan queries
- * mrp_film_mean_fwd_plan / mrp_film_mean_bwd_plan (enum mrp_agg_kernel, mrp_agg_plan); 21: v19 plus
+ * mrp_film_mean_fwd_plan / mrp_film_mean_bwd_plan (enum mrp_agg_kernel, mrp_agg_plan), and the FP8-message
+ * forwards mrp_film_mean_fwd_q / _q_plan, mrp_film_max_fwd_q, mrp_film_attn_fwd_q, mrp_film_wattn_fwd_q; 21: v19 plus
  * the streaming yardstick mrp_stream_copy, the device-scope stream join mrp_stream_join and the encoder's pose gradient (mrp_edge_encoder_bwd_pose
  * + workspace); 20: v19 plus a one-launch no-grad GCN layer
  * (mrp_gcn_fwd_fused), measured slower than the two launches it replaced and removed in 21

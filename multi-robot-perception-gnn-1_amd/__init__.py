@@ -12,6 +12,8 @@ from .aggregate import (EpilogueSpec, FilmMeanFunction, film_mean, film_mean_cat
                         pixel_strides, set_channels_last)
 from .aggregate import (dequantize_features, film_mean_fq, film_mean_q, film_mean_q_forward_into,  # noqa: F401
                         quantize_features)
+from .aggregate import (film_attn_q, film_attn_q_forward_into, film_max_fq, film_max_q,  # noqa: F401
+                        film_max_q_forward_into, film_wattn_q, film_wattn_q_forward_into)
 from .aggregate import (FilmMaxFunction, film_max, film_max_backward, film_max_cat,  # noqa: F401
                         film_max_forward_into)
 from .aggregate import (FilmWMeanCatFunction, FilmWMeanFunction, film_wmean, film_wmean_backward,  # noqa: F401

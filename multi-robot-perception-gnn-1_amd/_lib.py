@@ -30,6 +30,9 @@ EXPORTED_SYMBOLS = (
     "mrp_film_mean_bwd_plan",
     "mrp_film_mean_fwd_q",
     "mrp_film_mean_fwd_q_plan",
+    "mrp_film_max_fwd_q",
+    "mrp_film_attn_fwd_q",
+    "mrp_film_wattn_fwd_q",
     "mrp_film_mean_bwd_workspace",
     "mrp_film_mean_fwd_cl",
     "mrp_film_mean_bwd_cl",
@@ -243,6 +246,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         fn = getattr(lib, name)
         fn.argtypes = args[:at] + [_I32] + args[at:]
         fn.restype = ctypes.c_int
+    # FP8 messages, receiver side: qdtype, xq, stride, x_scale, then out_dtype (max) or dtype, query, stride
+    # (attention), then the typed entry's list from gb on (the attention forms: the multi-head one's)
+    lib.mrp_film_max_fwd_q.argtypes = [_I32, _P, _I64, _P, _I32] + lib.mrp_film_max_fwd.argtypes[3:]
+    lib.mrp_film_max_fwd_q.restype = ctypes.c_int
+    lib.mrp_film_attn_fwd_q.argtypes = [_I32, _P, _I64, _P, _I32, _P, _I64] + lib.mrp_film_attn_fwd_mh.argtypes[3:]
+    lib.mrp_film_attn_fwd_q.restype = ctypes.c_int
+    lib.mrp_film_wattn_fwd_q.argtypes = [_I32, _P, _I64, _P, _I32, _P, _I64] + lib.mrp_film_wattn_fwd_mh.argtypes[3:]
+    lib.mrp_film_wattn_fwd_q.restype = ctypes.c_int
     lib.mrp_film_attn_workspace_mh.argtypes = [_I32] * 9
     lib.mrp_film_attn_workspace_mh.restype = ctypes.c_int64
     lib.mrp_film_wattn_workspace_mh.argtypes = [_I32] * 9

@@ -582,7 +582,8 @@ def film_mean_cat(x: torch.Tensor, gb: Optional[torch.Tensor], csr: GraphCSR, mo
 # ``film_mean_fq`` is the differentiable fake-quant route on the existing fp32 kernels, with the same forward
 # bits.  OCP FP8 only (``torch.float8_e4m3fn`` / ``torch.float8_e5m2``), never the FNUZ encodings.  Not
 # provided: pixel-major FP8 kernels (a channels_last FP8 tensor is made NCHW-contiguous first), FP8 for
-# film_max / film_attn, FP8 outputs (quantising is left to torch: ``quantize_features``), FP8 backward.
+# film_wmean, FP8 outputs (quantising is left to torch: ``quantize_features``), FP8 backward.  The max and
+# attention reducers on FP8 messages: ``film_max_q`` / ``film_attn_q`` / ``film_wattn_q`` at the end of this file.
 # ---------------------------------------------------------------------------------------------------------
 #: fmt -> (torch dtype, largest finite value, enum mrp_qdtype)
 QUANT_FORMATS = {"e4m3": (torch.float8_e4m3fn, 448.0, _lib.QDTYPE_E4M3),
@@ -1691,3 +1692,208 @@ def film_wattn_mix(x: torch.Tensor, gb: torch.Tensor, w: torch.Tensor, csr: Grap
                    logits: bool = False, scale: Optional[float] = None, heads: int = 1) -> torch.Tensor:
     """``(1 - alpha) * film_wattn(x, ...) + alpha * x0`` (by torch ops: no fused epilogue for this reducer)."""
     return (1.0 - float(alpha)) * film_wattn(x, gb, w, csr, logits, scale, heads=heads) + float(alpha) * x0
+
+
+# ---------------------------------------------------------------------------------------------------------
+# FP8 messages for the max and attention reducers, receiver side (``mrp_film_max_fwd_q``,
+# ``mrp_film_attn_fwd_q``, ``mrp_film_wattn_fwd_q``).  A receiver holds its own features ``x`` at full precision
+# and is handed its neighbours' maps as FP8 codes ``xq`` with scales ``xscale`` (and, for the gated fusion, their
+# confidence maps ``w``).  The messages are formed from x^ = fl32(s * decode(q)), as in ``film_mean_q``; the
+# attention's query is x[v] — a robot's own maps never cross the link — so query and messages are two tensors:
+#
+#     film_max_q(xq, s, ..., out_dtype=T)  == film_max(dequantize_features(xq, s), ...).to(T)     bit for bit
+#     film_attn_q(x^, xq, s, ...)          == film_attn(x^, ...)   (x^ fp32), out and weights     bit for bit
+#     film_attn_q(x_T, ...)                == film_attn_q(x_T.float(), ...).to(T), the same weights
+#
+# Inference ops, as ``film_mean_q`` is.  ``film_max_fq`` is the differentiable fake-quant route of the max on the
+# existing kernels; there is no fake-quant attention: under the straight-through estimator the backward would
+# read the query from x and the sources from x^, which the backward kernels (one tensor for both) cannot.
+# ---------------------------------------------------------------------------------------------------------
+def _q_inputs(name: str, xq: torch.Tensor, xscale: Optional[torch.Tensor], csr: GraphCSR, *others):
+    """The host-side checks the FP8 receiver ops share (nothing here touches a device)."""
+    if not isinstance(xq, torch.Tensor) or xq.dtype not in _QDTYPES:
+        raise TypeError(f"xq must be float8_e4m3fn or float8_e5m2 (quantize_features), got "
+                        f"{getattr(xq, 'dtype', type(xq))}")
+    if xq.dim() != 4:
+        raise ValueError(f"quantised features must be (N, C, H, W), got {tuple(xq.shape)}")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (xscale,) + others):
+        raise RuntimeError(f"mrp_gnn: {name} is an inference op and would drop the gradient of its inputs; "
+                           "run it under torch.no_grad()"
+                           + (", or train through film_max_fq (same forward bits)" if name == "film_max_q" else ""))
+    n, C, H, W = xq.shape
+    if n != csr.num_nodes:
+        raise ValueError(f"xq has {n} nodes, graph has {csr.num_nodes}")
+    _q_scale(xscale, n, C)  # its shape: a host-side check
+
+
+def _q_device(xq: torch.Tensor, xscale: Optional[torch.Tensor]):
+    """(xq NCHW, its node stride, scale (N, C) fp32 contiguous or None) for the kernel."""
+    n, C, H, W = xq.shape
+    _require_device(xq, xscale)
+    xs = _dense_node_stride(xq)
+    if xs is None:  # channels_last or otherwise strided codes: made NCHW-contiguous first
+        xq = xq.contiguous()
+        xs = C * H * W
+    sc = _q_scale(xscale, n, C)
+    if sc is not None:
+        sc = sc.float().contiguous()
+    return xq, xs, sc
+
+
+def film_max_q_forward_into(xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor, csr: GraphCSR,
+                            out: torch.Tensor, logits: bool = False) -> torch.Tensor:
+    """:func:`film_max_q` into ``out`` (N, C, H, W) fp32 / bf16 / fp16 — which may be a strided view with a
+    contiguous block per node, such as the second half of a ``torch.cat((h, g_h), 1)`` buffer."""
+    _check_max_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    _q_inputs("film_max_q", xq, xscale, csr, gb)
+    n, C, H, W = xq.shape
+    if out.dim() != 4 or tuple(out.shape) != (n, C, H, W):
+        raise ValueError(f"out must be {(n, C, H, W)}, got {tuple(out.shape)}")
+    if out.dtype not in FEATURE_DTYPES:
+        raise TypeError(f"out must be float32, bfloat16 or float16 (FP8 outputs are not provided), got {out.dtype}")
+    os_ = node_stride(out)
+    if os_ is None:
+        raise ValueError("out must have a contiguous C*H*W block per node")
+    _require_device(out)
+    xq, xs, sc = _q_device(xq, xscale)
+    gb = _max_gb(gb, csr, C)
+    name, code = _QDTYPES[xq.dtype]
+    lib = _lib.load_library()
+    with torch.cuda.device(xq.device):
+        rc = lib.mrp_film_max_fwd_q(code, _ptr(xq), xs, _ptr(sc), FEATURE_DTYPES[out.dtype],
+                                    *_graph_args(gb, csr, C, H * W, _lib.GB_LOGITS if logits else 0), _ptr(out), os_,
+                                    _stream(xq.device))
+    _lib.check(rc, "mrp_film_max_fwd_q")
+    PATH_COUNTS["max_fwd_q_" + name] += 1
+    return out
+
+
+def film_max_q(xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor, csr: GraphCSR,
+               logits: bool = False, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """:func:`film_max` of FP8 messages, read natively (``mrp_film_max_fwd_q``).
+
+    xq: (N, C, H, W) ``torch.float8_e4m3fn`` / ``torch.float8_e5m2`` codes; xscale: their fp32 scales, (N,),
+    (N, 1) or (N, C) (``quantize_features``), or None; gb / csr / logits as :func:`film_max`.  Returns the
+    aggregate in ``out_dtype`` (fp32, bf16 or fp16): bit-equal to ``film_max(dequantize_features(xq, xscale),
+    ...)`` cast once.  An inference op: under grad mode with an input that requires grad it raises
+    (:func:`film_max_fq` is the differentiable route)."""
+    if isinstance(xq, torch.Tensor) and xq.dim() != 4:
+        raise ValueError(f"quantised features must be (N, C, H, W), got {tuple(xq.shape)}")
+    if out_dtype not in FEATURE_DTYPES:
+        raise TypeError(f"out_dtype must be float32, bfloat16 or float16, got {out_dtype}")
+    if not isinstance(xq, torch.Tensor) or xq.dtype not in _QDTYPES:
+        raise TypeError(f"xq must be float8_e4m3fn or float8_e5m2 (quantize_features), got "
+                        f"{getattr(xq, 'dtype', type(xq))}")
+    out = torch.empty(xq.shape, device=xq.device, dtype=out_dtype)
+    return film_max_q_forward_into(xq, xscale, gb, csr, out, logits)
+
+
+def film_max_fq(x: torch.Tensor, gb: torch.Tensor, csr: GraphCSR, fmt: str = "e4m3", per: str = "channel",
+                logits: bool = False) -> torch.Tensor:
+    """The differentiable fake-quant route of :func:`film_max_q`, on the existing kernels: x is quantised
+    (``quantize_features``), x^ formed in fp32 (``dequantize_features``) with a straight-through estimator (the
+    gradient reaches x as if x^ = x), and the fp32 ``FilmMaxFunction`` run on it; the result is cast to
+    ``x.dtype``.  Its forward bits equal ``film_max_q(*quantize_features(x, fmt, per), ..., out_dtype=x.dtype)``."""
+    _check_max_degree(csr)
+    _check_x(x)
+    xq, s = quantize_features(x, fmt, per)
+    xh = dequantize_features(xq, s)
+    if torch.is_grad_enabled() and x.requires_grad:
+        xh = _StraightThrough.apply(x, xh)
+    return FilmMaxFunction.apply(xh, gb, csr, _lib.GB_LOGITS if logits else 0).to(x.dtype)
+
+
+def _attn_q_forward_into(name: str, x, xq, xscale, gb, w, csr: GraphCSR, out, logits, scale, heads, attn, rate):
+    """The forward behind film_attn_q (w None) and film_wattn_q; returns (attn, rate)."""
+    _check_attn_degree(csr)  # a host-side property of the graph: checked before anything touches a device
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("the receiver's own features x must be (N, C, H, W) float32, bfloat16 or float16")
+    _q_inputs(name, xq, xscale, csr, x, gb, w)
+    n, C, H, W = xq.shape
+    if tuple(x.shape) != (n, C, H, W):
+        raise ValueError(f"x must have the messages' shape {(n, C, H, W)}, got {tuple(x.shape)}")
+    heads = _check_heads(heads, C)
+    scale = _attn_scale(scale, C // heads)
+    _require_device(x, out, attn, rate if isinstance(rate, torch.Tensor) else None)
+    xq, xs, sc = _q_device(xq, xscale)
+    x, qs = _as_node_major(x)  # a channels_last x is copied to NCHW here
+    os_ = node_stride(out)
+    if os_ is None or tuple(out.shape) != (n, C, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {(n, C, H, W)} {x.dtype} with a contiguous block per node")
+    if w is not None:
+        w, wst = _wmean_weights(w, n, H, W)
+    gb = _attn_gb(gb, csr, C)
+    wshape = _weights_shape(csr, H * W, heads)
+    bufs = []
+    for what, t in (("attn", attn), ("rate", rate)):
+        if t is None or t is False:
+            t = None if what == "rate" else torch.empty(wshape, device=x.device, dtype=torch.float32)
+        elif t is True:
+            t = torch.empty(wshape, device=x.device, dtype=torch.float32)
+        elif tuple(t.shape) != wshape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {wshape} float32 tensor")
+        bufs.append(t)
+    attn, rate = bufs
+    if w is None:
+        rate = None
+    fname, code = _QDTYPES[xq.dtype]
+    lib = _lib.load_library()
+    ga = _graph_args(gb, csr, C, H * W, _lib.GB_LOGITS if logits else 0)
+    head = (code, _ptr(xq), xs, _ptr(sc), FEATURE_DTYPES[x.dtype], _ptr(x), qs, ga[0])
+    with torch.cuda.device(x.device):
+        if w is None:
+            rc = lib.mrp_film_attn_fwd_q(*head, *ga[1:], heads, _ptr(out), os_, scale, _ptr(attn), None, 0,
+                                         _stream(x.device))
+        else:
+            rc = lib.mrp_film_wattn_fwd_q(*head, _ptr(w), wst, *ga[1:], heads, _ptr(out), os_, scale, _ptr(attn),
+                                          _ptr(rate), None, 0, _stream(x.device))
+    _lib.check(rc, "mrp_film_attn_fwd_q" if w is None else "mrp_film_wattn_fwd_q")
+    PATH_COUNTS[("attn" if w is None else "wattn") + ("_fwd_q_" if heads == 1 else "_fwd_q_mh_") + fname] += 1
+    return attn, rate
+
+
+def film_attn_q_forward_into(x: torch.Tensor, xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor,
+                             csr: GraphCSR, out: torch.Tensor, logits: bool = False, scale: Optional[float] = None,
+                             heads: int = 1, attn: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`film_attn_q` into ``out`` (N, C, H, W) of x's dtype — which may be a strided view such as the second
+    half of a ``torch.cat((h, g_h), 1)`` buffer; returns the weights (written into ``attn`` if given)."""
+    return _attn_q_forward_into("film_attn_q", x, xq, xscale, gb, None, csr, out, logits, scale, heads, attn, None)[0]
+
+
+def film_attn_q(x: torch.Tensor, xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor, csr: GraphCSR,
+                logits: bool = False, scale: Optional[float] = None, heads: int = 1, return_weights: bool = False):
+    """:func:`film_attn` on the receiver's side of an FP8 link (``mrp_film_attn_fwd_q``): the messages
+    ``gamma_e * x^[src] + beta_e`` are formed from the codes ``xq`` (N, C, H, W) ``torch.float8_e4m3fn`` /
+    ``torch.float8_e5m2`` and their scales ``xscale`` ((N,), (N, 1), (N, C) or None), and scored by the receiver's
+    own, unquantised features ``x`` (N, C, H, W) fp32, bf16 or fp16, whose dtype is the output's.  gb / csr /
+    logits / scale / heads / return_weights as :func:`film_attn`.  Row v of ``x`` is read as v's query only: it
+    is nobody's message.  An inference op: under grad mode with an input that requires grad it raises."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("the receiver's own features x must be (N, C, H, W) float32, bfloat16 or float16")
+    out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+    attn = film_attn_q_forward_into(x, xq, xscale, gb, csr, out, logits, scale, heads)
+    return (out, attn) if return_weights else out
+
+
+def film_wattn_q_forward_into(x: torch.Tensor, xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor,
+                              w: torch.Tensor, csr: GraphCSR, out: torch.Tensor, logits: bool = False,
+                              scale: Optional[float] = None, heads: int = 1, attn: Optional[torch.Tensor] = None,
+                              rate=False):
+    """:func:`film_wattn_q` into ``out`` (as :func:`film_attn_q_forward_into`); returns ``(attn, rate)``, rate
+    (the softmax's response to each sender's weight) only with ``rate=True`` or a tensor to write into."""
+    if w is None:
+        raise ValueError("film_wattn_q needs the sender maps w (N, H, W)")
+    return _attn_q_forward_into("film_wattn_q", x, xq, xscale, gb, w, csr, out, logits, scale, heads, attn, rate)
+
+
+def film_wattn_q(x: torch.Tensor, xq: torch.Tensor, xscale: Optional[torch.Tensor], gb: torch.Tensor,
+                 w: torch.Tensor, csr: GraphCSR, logits: bool = False, scale: Optional[float] = None, heads: int = 1,
+                 return_weights: bool = False):
+    """:func:`film_wattn` on the receiver's side of an FP8 link (``mrp_film_wattn_fwd_q``): :func:`film_attn_q`
+    gated and weighted by the received sender maps ``w`` (N, H, W) fp32 >= 0.  A sender that is silent at a
+    pixel is never read there, whatever its codes.  With ``w == 1`` it gives :func:`film_attn_q`'s bits."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in FEATURE_DTYPES:
+        raise ValueError("the receiver's own features x must be (N, C, H, W) float32, bfloat16 or float16")
+    out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+    attn, _ = film_wattn_q_forward_into(x, xq, xscale, gb, w, csr, out, logits, scale, heads)
+    return (out, attn) if return_weights else out

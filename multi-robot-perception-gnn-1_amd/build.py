@@ -21,6 +21,8 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in ("film_mean_bwd_1_8.hip", "
                                                     "film_attn_mh_bwd_f16.hip", "film_attn_mh_fwd.hip",
                                                     "film_wattn_mh_bwd.hip", "film_wattn_mh_bwd_bf16.hip",
                                                     "film_wattn_mh_bwd_f16.hip", "film_wattn_mh_fwd.hip",
+                                                    "film_attn_fwd_q.hip", "film_wattn_fwd_q.hip",
+                                                    "film_max_fwd_q.hip",
                                                     "film_wmean_bwd.hip", "film_wmean_bwd_bf16.hip",
                                                     "film_wmean_bwd_f16.hip", "film_wmean_fwd.hip",
                                                     "film_mean_fwd.hip",

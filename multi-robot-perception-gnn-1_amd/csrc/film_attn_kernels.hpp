@@ -333,6 +333,150 @@ __device__ __forceinline__ void attn_scores(const AttnArgs& m, const AttnLds& L,
   }
 }
 
+// ---------------------------------------------------------------------------
+// FP8 messages, receiver side (film_attn_fwd with TX = q8_t).  The messages are x^[u,c,p] = fl32(s[u,c] * decode(xq[u,c,p])):
+// codes of format a.qfmt (E4M3 / E5M2, never FNUZ) at a.x, node stride a.xs, with per-(source node, channel)
+// scales a.xscale (rows of C, NULL: all 1).  The receiver's own features never crossed the link: the query of
+// destination v is q[v,c,p] of type T, a second tensor.  Wave w stages exactly the nodes that are its own
+// destinations and a lane owns its pixel, so the chunk's query values stay in that wave's registers (CK x
+// kAttnDpw of them) and LDS holds what it always held.  From the staged plane on the statements are
+// film_attn_fwd's.
+// ---------------------------------------------------------------------------
+template <bool WGT, bool MH>
+struct AttnQArgs : AttnKernelArgs<WGT, MH> {
+  const void* q;  // (nodes, C, P) own features of type T, node stride qs
+  int64_t qs;
+};
+// film_attn_fwd's argument block for messages of type TX
+template <bool WGT, bool MH, typename TX>
+using AttnFwdArgs =
+    std::conditional_t<std::is_same<TX, q8_t>::value, AttnQArgs<WGT, MH>, AttnKernelArgs<WGT, MH>>;
+
+// MH: what a single-head launch on the head's channel slice of the codes, the scales and the query would get.
+template <typename T, bool WGT>
+__device__ __forceinline__ void attn_head_rebase_q(AttnQArgs<WGT, true>& m) {
+  AggArgs& a = m.a;
+  const int64_t k = blockIdx.y;
+  const int64_t xoff = k * a.C * a.P, eoff = k * m.E * a.P;
+  a.x = static_cast<const q8_t*>(a.x) + xoff;
+  m.q = static_cast<const T*>(m.q) + xoff;
+  a.out = static_cast<T*>(a.out) + xoff;
+  if (a.gb != nullptr) a.gb += k * a.C * 2;
+  if (a.xscale != nullptr) a.xscale += k * a.C;
+  if (m.attn != nullptr) m.attn += eoff;
+  if constexpr (WGT) {
+    if (m.rate != nullptr) m.rate += eoff;
+  }
+}
+
+// One code, decoded by load_frag's hardware conversions and multiplied once by its scale.
+__device__ __forceinline__ float attn_decode(uint8_t code, int fmt, float s) {
+  const f2 v = fmt == MRP_QDTYPE_E5M2 ? __builtin_amdgcn_cvt_pk_f32_bf8((int)code, false)
+                                      : __builtin_amdgcn_cvt_pk_f32_fp8((int)code, false);
+  return __fmul_rn(s, v.x);
+}
+
+template <int CK, typename T>
+struct AttnChunkQ {
+  uint8_t x[CK * kAttnDpw];  // codes as stored: decoded when put
+  float sc[CK * kAttnDpw];   // their scales (wave-uniform)
+  T q[CK * kAttnDpw];        // the query of the wave's destinations
+  float2 w[CK];
+};
+
+// attn_fetch for codes.  QUERY: also the query values (sweep A alone reads them).  gbC: the channels of gb's and
+// the scales' rows.
+template <int CK, typename T, bool QUERY, typename Args>
+__device__ __forceinline__ void attn_fetch_q(const Args& m, int node0, int n, int c0, int p, bool pin, int my_e,
+                                             AttnChunkQ<CK, T>& r, int gbC) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6;
+  const int wu = __builtin_amdgcn_readfirstlane(wave);  // the scales' addresses are scalar
+  const int ck = min(CK, a.C - c0);  // <= 0 past the last chunk: nothing is loaded
+  const q8_t* xb = static_cast<const q8_t*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P + p;
+  const T* qb = static_cast<const T*>(m.q) + (int64_t)node0 * m.qs + (int64_t)c0 * a.P + p;
+  const float* sb = a.xscale != nullptr ? a.xscale + (int64_t)node0 * gbC + c0 : nullptr;
+#pragma unroll
+  for (int cl = 0; cl < CK; ++cl) {
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int u = wave + kAttnWaves * i;
+      uint8_t xv = 0;
+      T qv = (T)0.f;
+      if (cl < ck && u < n && pin) {
+        xv = xb[(int64_t)u * a.xs + (int64_t)cl * a.P].b;
+        if constexpr (QUERY) qv = qb[(int64_t)u * m.qs + (int64_t)cl * a.P];
+      }
+      r.x[cl * kAttnDpw + i] = xv;
+      r.q[cl * kAttnDpw + i] = qv;
+      const int uu = wu + kAttnWaves * i;
+      r.sc[cl * kAttnDpw + i] = (sb != nullptr && cl < ck && uu < n) ? sb[(int64_t)uu * gbC + cl] : 1.f;
+    }
+    float2 w = make_float2(0.f, 0.f);
+    if (cl < ck && my_e >= 0) w = *reinterpret_cast<const float2*>(a.gb + ((int64_t)my_e * gbC + c0 + cl) * 2);
+    r.w[cl] = w;
+  }
+}
+
+// attn_put for codes: decoded and scaled here, once per (node, channel, pixel).
+template <int CK, typename T, typename Args>
+__device__ __forceinline__ void attn_put_q(const Args& m, const AttnLds& L, int n, int my_e,
+                                           const AttnChunkQ<CK, T>& r) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+#pragma unroll
+  for (int cl = 0; cl < CK; ++cl) {
+#pragma unroll
+    for (int i = 0; i < kAttnDpw; ++i) {
+      const int u = wave + kAttnWaves * i;
+      if (u < n)
+        L.X[(cl * a.nmax + u) * kAttnTile + lane] =
+            attn_decode(r.x[cl * kAttnDpw + i], a.qfmt, r.sc[cl * kAttnDpw + i]);
+    }
+    if ((int)threadIdx.x < n * kAttnSlots) {
+      float2 w = r.w[cl];
+      if (a.logits && my_e >= 0) w = make_float2(sigmoidf(w.x), sigmoidf(w.y));
+      L.W[cl * a.nmax * kAttnSlots + threadIdx.x] = w;
+    }
+  }
+  __syncthreads();
+}
+
+// attn_scores with the query in registers: acc[i][j] += q_i[c,p] * m_j[c,p], the same ascending chain.  A
+// destination's CK query values are one register vector, the chunk channel a wave-uniform dynamic extract (as
+// film_max's sources are): the channel loop stays rolled, as attn_scores' is.
+template <int CK>
+struct AttnQVec {
+  typedef float type __attribute__((ext_vector_type(CK)));
+};
+template <int CK, int KS, typename Args>
+__device__ __forceinline__ void attn_scores_q(const Args& m, const AttnLds& L, int n, int ck,
+                                              const typename AttnQVec<CK>::type (&q)[kAttnDpw],
+                                              float (&acc)[kAttnDpw][KS]) {
+  const AggArgs& a = m.a;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int i = 0; i < kAttnDpw; ++i) {
+    const int v = wave + kAttnWaves * i;
+    if (v >= n) continue;  // wave-uniform
+    const AttnRow r(L, v);
+    for (int cl = 0; cl < ck; ++cl) {
+      const float* Xc = L.X + cl * a.nmax * kAttnTile + lane;
+      const float2* Wc = L.W + cl * a.nmax * kAttnSlots + v * kAttnSlots;
+      const float qv = q[i][cl];
+      float2 w[KS];
+      float xu[KS];
+      attn_slots<KS>(Xc, Wc, r, w, xu);
+#pragma unroll
+      for (int jj = 0; jj < KS; ++jj) {
+        const float msg = __fadd_rn(__fmul_rn(w[jj].x, xu[jj]), w[jj].y);
+        acc[i][jj] = __fmaf_rn(qv, msg, acc[i][jj]);
+      }
+    }
+  }
+}
+
 // Sum over the wave's 64 lanes, valid in lane 63: within rows of 16 by quad_perm, row_half_mirror and row_mirror,
 // then row 0 into 1 and 2 into 3 (row_bcast15), then rows 0-1 into 2-3 (row_bcast31).  DPP only: no LDS round
 // trip, a fixed order.
@@ -354,9 +498,19 @@ __device__ __forceinline__ float wave_sum63(float x) {
 // Forward.  Workgroup = graph x pixel tile.  KS: compiled slots per destination (4, 8 or 16; the launcher picks
 // KS >= the graph kind's in-degree bound).
 // ---------------------------------------------------------------------------
-template <typename T, int KS, bool WGT = false, bool MH = false>
-__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnKernelArgs<WGT, MH> m) {
-  if constexpr (MH) attn_head_rebase<T, WGT>(m);
+// TX: the storage type of the messages.  TX = T: they are x itself, and x[v] is also v's query (mrp_film_attn_fwd and
+// its kin).  TX = q8_t: FP8 codes with per-(source node, channel) scales, and the query is a tensor of its own
+// (a.x holds the codes, m.q the receiver's own features; T is their type and the output's: mrp_film_attn_fwd_q /
+// mrp_film_wattn_fwd_q).
+template <typename T, int KS, bool WGT = false, bool MH = false, typename TX = T>
+__global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnFwdArgs<WGT, MH, TX> m) {
+  constexpr bool kQ = std::is_same<TX, q8_t>::value;
+  if constexpr (MH) {
+    if constexpr (kQ)
+      attn_head_rebase_q<T, WGT>(m);
+    else
+      attn_head_rebase<T, WGT>(m);
+  }
   const AggArgs& a = m.a;
   extern __shared__ float4 smem_f4[];
   const AttnLds L(smem_f4, a.nmax, kAttnFwdChunk, false);
@@ -372,7 +526,10 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnKernelArgs<WGT, MH> 
   attn_tables(m, L, b, node0, n);
   constexpr int CK = kAttnFwdChunk;
   const int my_e = (int)threadIdx.x < n * kAttnSlots ? L.slot_e[threadIdx.x] : -1;
-  AttnChunk<CK, false, T> next;
+  std::conditional_t<kQ, AttnChunkQ<CK, T>, AttnChunk<CK, false, T>> next;
+  if constexpr (kQ)
+    attn_fetch_q<CK, T, true>(m, node0, n, 0, p, pin, my_e, next, attn_gb_channels<MH>(m));
+  else
   attn_fetch<CK, false, T, MH>(m, node0, n, 0, p, pin, my_e, next, false, attn_gb_channels<MH>(m));
 
   float s[kAttnDpw][KS];
@@ -383,10 +540,24 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnKernelArgs<WGT, MH> 
 
   // sweep A: the scores, each an ascending chain over the channels
   for (int c0 = 0; c0 < a.C; c0 += CK) {
+    if constexpr (kQ) {
+      attn_put_q<CK, T>(m, L, n, my_e, next);
+      typename AttnQVec<CK>::type q[kAttnDpw];  // this chunk's query values, kept while the next chunk is fetched
+#pragma unroll
+      for (int cl = 0; cl < CK; ++cl)
+#pragma unroll
+        for (int i = 0; i < kAttnDpw; ++i) q[i][cl] = (float)next.q[cl * kAttnDpw + i];
+      if (c0 + CK < a.C)
+        attn_fetch_q<CK, T, true>(m, node0, n, c0 + CK, p, pin, my_e, next, attn_gb_channels<MH>(m));
+      else  // wraps: sweep B's first, which scores nothing
+        attn_fetch_q<CK, T, false>(m, node0, n, 0, p, pin, my_e, next, attn_gb_channels<MH>(m));
+      attn_scores_q<CK, KS>(m, L, n, min(CK, a.C - c0), q, s);
+    } else {
     attn_put<CK, false, T>(m, L, n, my_e, next);
     attn_fetch<CK, false, T, MH>(m, node0, n, c0 + CK < a.C ? c0 + CK : 0, p, pin, my_e, next, false,
                                 attn_gb_channels<MH>(m));  // wraps: sweep B's first
     attn_scores<false, KS>(m, L, n, min(CK, a.C - c0), s);
+    }
   }
 
   // softmax over the row's entries, in registers; s becomes the weights
@@ -463,8 +634,13 @@ __global__ void __launch_bounds__(kBlock) film_attn_fwd(AttnKernelArgs<WGT, MH> 
   // sweep B: out = sum_j a_j m_j in slot order
   for (int c0 = 0; c0 < a.C; c0 += CK) {
     const int ck = min(CK, a.C - c0);
+    if constexpr (kQ) {
+      attn_put_q<CK, T>(m, L, n, my_e, next);
+      attn_fetch_q<CK, T, false>(m, node0, n, c0 + CK, p, pin, my_e, next, attn_gb_channels<MH>(m));
+    } else {
     attn_put<CK, false, T>(m, L, n, my_e, next);
     attn_fetch<CK, false, T, MH>(m, node0, n, c0 + CK, p, pin, my_e, next, false, attn_gb_channels<MH>(m));
+    }
 #pragma unroll
     for (int i = 0; i < kAttnDpw; ++i) {
       const int v = wave + kAttnWaves * i;
@@ -783,6 +959,48 @@ hipError_t launch_wattn_mh_fwd(int32_t dtype, const mrp::AttnMhArgs<true>& m, in
 // film_attn_gw_reduce (film_attn_mh_fwd.hip): grad_w (nodes, P), node stride gwst, from the heads' partials
 hipError_t launch_attn_gw_reduce(const float* part, int heads, int32_t nodes, int32_t P, float* gw, int64_t gwst,
                                  hipStream_t st);
+
+// the FP8-message forwards (film_attn_fwd_q.hip: WGT = false, film_wattn_fwd_q.hip: WGT = true); heads = 1 for the
+// single-head argument blocks
+hipError_t launch_attn_fwd_q(int32_t dtype, const mrp::AttnQArgs<false, false>& m, int ks, size_t lds, int64_t grid,
+                             int heads, hipStream_t st);
+hipError_t launch_attn_fwd_q(int32_t dtype, const mrp::AttnQArgs<false, true>& m, int ks, size_t lds, int64_t grid,
+                             int heads, hipStream_t st);
+hipError_t launch_attn_fwd_q(int32_t dtype, const mrp::AttnQArgs<true, false>& m, int ks, size_t lds, int64_t grid,
+                             int heads, hipStream_t st);
+hipError_t launch_attn_fwd_q(int32_t dtype, const mrp::AttnQArgs<true, true>& m, int ks, size_t lds, int64_t grid,
+                             int heads, hipStream_t st);
+
+template <typename T, bool WGT, bool MH>
+hipError_t launch_attn_fwd_q_t(const mrp::AttnQArgs<WGT, MH>& m, int ks, size_t lds, int64_t grid, int heads,
+                               hipStream_t st) {
+  const dim3 g((unsigned)grid, (unsigned)heads), block(mrp::kBlock);
+  if (ks == 4)
+    hipLaunchKernelGGL((mrp::film_attn_fwd<T, 4, WGT, MH, mrp::q8_t>), g, block, lds, st, m);
+  else if (ks == 8)
+    hipLaunchKernelGGL((mrp::film_attn_fwd<T, 8, WGT, MH, mrp::q8_t>), g, block, lds, st, m);
+  else
+    hipLaunchKernelGGL((mrp::film_attn_fwd<T, 16, WGT, MH, mrp::q8_t>), g, block, lds, st, m);
+  return hipGetLastError();
+}
+
+template <bool WGT, bool MH>
+hipError_t launch_attn_fwd_q_dtype(int32_t dtype, const mrp::AttnQArgs<WGT, MH>& m, int ks, size_t lds, int64_t grid,
+                                   int heads, hipStream_t st) {
+  switch (dtype) {
+    case MRP_DTYPE_F32: return launch_attn_fwd_q_t<float, WGT, MH>(m, ks, lds, grid, heads, st);
+    case MRP_DTYPE_BF16: return launch_attn_fwd_q_t<mrp::bf16_t, WGT, MH>(m, ks, lds, grid, heads, st);
+    default: return launch_attn_fwd_q_t<mrp::f16_t, WGT, MH>(m, ks, lds, grid, heads, st);
+  }
+}
+
+// The forward both FP8-message entry points share (film_attn_fwd_q.hip); weighted: mrp_film_wattn_fwd_q.
+int attn_fwd_q(bool weighted, int32_t qdtype, const void* xq, int64_t xq_node_stride, const float* x_scale,
+               int32_t dtype, const void* query, int64_t query_node_stride, const float* gb, const float* w,
+               int64_t w_node_stride, const int32_t* indptr, const int32_t* src, const int32_t* eid,
+               const int32_t* graph_off, int32_t num_graphs, int32_t max_nodes, int32_t graph_kind, int32_t num_nodes,
+               int32_t num_edges, int32_t C, int32_t P, int32_t flags, int32_t heads, void* out,
+               int64_t out_node_stride, float scale, float* attn, float* rate, int64_t workspace_bytes, void* stream);
 
 constexpr int kMaxGridY = 65535;  // the head factor of the grid
 

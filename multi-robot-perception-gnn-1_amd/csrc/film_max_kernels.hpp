@@ -126,8 +126,11 @@ struct MaxVec {
 // Forward.  Workgroup = graph x channel block x plane segment, as film_fwd.
 // NT: compiled node capacity (4, 8 or 16); the graph's node count n <= NT is wave-uniform at run time.
 // ---------------------------------------------------------------------------
-template <int NT, int VEC, typename T>
+// TX: the storage type of the gathered input x alone (out keeps T).  TX = q8_t: FP8 messages, widened and scaled in
+// load_frag (a.qfmt, a.xscale) as in film_fwd; the arithmetic from there on is TX = T's (mrp_film_max_fwd_q).
+template <int NT, int VEC, typename T, typename TX = T>
 __global__ void __launch_bounds__(kBlock) film_max_fwd(MaxArgs m) {
+  constexpr bool kQ = std::is_same<TX, q8_t>::value;
   const AggArgs& a = m.a;
   constexpr int WS = MaxLds<NT>::WS;
   extern __shared__ float4 smem_f4[];
@@ -150,9 +153,17 @@ __global__ void __launch_bounds__(kBlock) film_max_fwd(MaxArgs m) {
   const int li = threadIdx.x - grp * a.lpc;
   const int c = c0 + grp;
   const bool active = grp < a.cpb && c < a.C;
-  const T* xb = static_cast<const T*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
+  const TX* xb = static_cast<const TX*>(a.x) + (int64_t)node0 * a.xs + (int64_t)c0 * a.P;
   T* ob = static_cast<T*>(a.out) + (int64_t)node0 * a.os + (int64_t)c0 * a.P;
   const uint32_t lane_plane = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(T);
+  const uint32_t lane_plane_x = (uint32_t)grp * (uint32_t)a.P * (uint32_t)sizeof(TX);
+  // FP8 messages: the scales of this lane's channel for the graph's nodes, read once per workgroup
+  float xsc[kQ ? NT : 1];
+  if constexpr (kQ) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u)
+      xsc[u] = (active && u < n && a.xscale != nullptr) ? a.xscale[(int64_t)(node0 + u) * a.C + c] : 1.f;
+  }
 
   // 16-wide register vectors whatever NT (up to 4-element slices: 64 registers): only those are indexed
   // through s_set_gpr_idx; an 8-wide vector's extract becomes a chain of 8 selects per element (header comment)
@@ -164,8 +175,12 @@ __global__ void __launch_bounds__(kBlock) film_max_fwd(MaxArgs m) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       if (u >= n) break;  // wave-uniform
-      const Frag<VEC> f = load_frag<VEC, true>(
-          at_bytes(xb + (int64_t)u * a.xs, lane_plane + (uint32_t)jj * VEC * (uint32_t)sizeof(T)));
+      const TX* px = at_bytes(xb + (int64_t)u * a.xs, lane_plane_x + (uint32_t)jj * VEC * (uint32_t)sizeof(TX));
+      Frag<VEC> f;
+      if constexpr (kQ)
+        f = load_frag<VEC, true>(px, a.qfmt, xsc[u]);
+      else
+        f = load_frag<VEC, true>(px);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) xs[k][u] = f.v[k];
     }

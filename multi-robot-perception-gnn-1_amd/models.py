@@ -41,7 +41,10 @@ over an 8-bit link, with one scale per (node, channel) (``opt.gcn_message_scale=
 per node (``'node'``); the layer's own-feature terms (cat half, residual, compress input) use the
 unquantised features.  In a single-GPU simulation the quantise pass costs more than the aggregation saves:
 the option exists to evaluate and train models for 8-bit links.  The saving belongs to a receiver that is
-handed FP8 buffers (:func:`aggregate.film_mean_q`).  See :meth:`GCN._aggregate_q`.
+handed FP8 buffers (:func:`aggregate.film_mean_q`).  See :meth:`GCN._aggregate_q`.  That receiver's layer is
+:meth:`GCN.forward_received` / :meth:`GCN.forward_cat_received`: own features at full precision, received codes,
+scales and (``film_wattn``) confidence maps in, for every ``gcn_mode`` — the max and attention reducers included,
+which ``gcn_message_dtype`` itself still refuses.
 
 ``opt.gcn_confidence`` (default off: nothing changes, no new parameters): every GCN layer owns a 1x1 head
 ``confidence = nn.Conv2d(C, 1, 1)``; each sender attaches ``w = sigmoid(confidence(x))`` to its feature map and
@@ -60,6 +63,7 @@ import torch
 import torch.nn as nn
 
 from .aggregate import (film_mean_fq, film_mean_q, film_mean_q_forward_into, quantize_features)
+from .aggregate import film_attn_q_forward_into, film_max_q_forward_into, film_wattn_q_forward_into
 from .aggregate import film_wmean, film_wmean_cat, film_wmean_mix, film_wmean_residual
 from .aggregate import film_wattn, film_wattn_cat, film_wattn_mix, film_wattn_residual
 from .aggregate import (film_attn, film_attn_cat, film_attn_mix, film_attn_residual, film_max, film_max_cat,
@@ -354,6 +358,55 @@ class GCN(_PackedImages, nn.Module):
             return film_attn_cat(x, z, g.csr(x.device), logits=True, scale=self._attn_scale(), heads=self._attn_heads())
         return film_mean_cat(x, z, g.csr(x.device), mode, logits=True)
 
+    def _received(self, g, x, xq, xscale, weights, out):
+        """The aggregate of received FP8 messages into ``out`` (N, C, H, W) of x's dtype, for ``opt.gcn_mode``."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("mrp_gnn: GCN.forward_received is inference-only (the FP8 receiver kernels have no "
+                               "backward); run it under torch.no_grad()")
+        if self._return_mode() == "input":
+            raise ValueError("forward_received with gcn_return='input': no message is aggregated")
+        mode = _opt(self.opt, "gcn_mode", "film_mean")
+        if weights is not None and mode != "film_wattn":
+            raise ValueError(f"forward_received takes weights= for gcn_mode='film_wattn' only, not {mode!r}")
+        if x.dim() != 4 or tuple(xq.shape) != tuple(x.shape):
+            raise ValueError(f"x {tuple(x.shape)} and xq {tuple(xq.shape)} must be the same (N, C, H, W)")
+        csr = g.csr(x.device)
+        z = None if mode == "copy_mean" else self.edge_encoder.logits(g.edata["pose"])
+        if mode == "film_max":
+            return film_max_q_forward_into(xq, xscale, z, csr, out, logits=True)
+        if mode in ("film_attn", "film_wattn"):
+            kw = dict(logits=True, scale=self._attn_scale(), heads=self._attn_heads())
+            if weights is not None:
+                film_wattn_q_forward_into(x, xq, xscale, z, weights, csr, out, **kw)
+            else:
+                film_attn_q_forward_into(x, xq, xscale, z, csr, out, **kw)
+            return out
+        return film_mean_q_forward_into(xq, xscale, z, csr, out, mode, logits=True)
+
+    def forward_received(self, g, x: torch.Tensor, xq: torch.Tensor, xscale: torch.Tensor = None,
+                         weights: torch.Tensor = None) -> torch.Tensor:
+        """The layer of a robot that was handed FP8 buffers: the aggregate of the received messages ``xq``
+        (N, C, H, W) ``torch.float8_e4m3fn`` / ``torch.float8_e5m2`` with scales ``xscale`` ((N,), (N, 1), (N, C) or
+        None), in the dtype of the receiver-side own features ``x`` (N, C, H, W).  Every ``opt.gcn_mode``: the mean
+        modes through :func:`aggregate.film_mean_q`, ``film_max`` through :func:`aggregate.film_max_q` (neither
+        reads x beyond its dtype), ``film_attn`` / ``film_wattn`` through :func:`aggregate.film_attn_q` with x as
+        the query (``opt.gcn_attn_scale``, ``opt.gcn_attn_heads``), and ``film_wattn`` with ``weights=`` (the
+        received maps, (N, H, W) fp32) through :func:`aggregate.film_wattn_q`.  Inference-only; nothing is read
+        from ``opt.gcn_message_dtype`` (that option simulates the link on one GPU)."""
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=x.dtype)
+        return self._received(g, x, xq, xscale, weights, out)
+
+    def forward_cat_received(self, g, x: torch.Tensor, xq: torch.Tensor, xscale: torch.Tensor = None,
+                             weights: torch.Tensor = None) -> torch.Tensor:
+        """``torch.cat((x, self.forward_received(g, x, xq, xscale, weights)), 1)`` with the aggregate written
+        straight into the buffer's second half."""
+        if x.dim() != 4:
+            raise ValueError(f"x must be (N, C, H, W), got {tuple(x.shape)}")
+        n, C, H, W = x.shape
+        cat = torch.empty((n, 2 * C, H, W), device=x.device, dtype=x.dtype)
+        self._received(g, x, xq, xscale, weights, cat[:, C:])
+        cat[:, :C].copy_(x)
+        return cat
 
     def forward_cat_compress(self, g, feats: torch.Tensor, conv: nn.Conv2d,
                              weights: torch.Tensor = None) -> torch.Tensor:
